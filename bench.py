@@ -26,6 +26,12 @@ its own slice from a counter-based generator, rank 0 hashing the stitched band +
 that an N-rank run can be compared with the 1-rank run bit for bit.
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs DIR) and prints the line: `value`,
+`ms_per_step` and the roofline of the timed region.  Everything else it can measure or check -- the parity spot check
+against the oracle, the post-hoc kernel timing, the clock / power soak, the RO_PRECISION_F64 and station-shape legs, the
+streaming path, the CPU baselines, the other exchange legs of an N > 1 run and the result hashes -- runs with --full
+(and the --no-* options switch parts of it off).
 """
 import argparse
 import ctypes
@@ -92,16 +98,26 @@ def parse():
     p.add_argument("--no-streaming", action="store_true", help="skip the drop-in (Backend::process) streaming leg")
     p.add_argument("--stream-seconds", type=float, default=2.5, help="timed length of the streaming leg")
     p.add_argument("--no-legs", action="store_true",
-                   help="N > 1: skip the extra untimed-for-`value` runs with the other --gather modes (config.exchange_legs_rows_per_s)")
+                   help="--full, N > 1: skip the extra untimed-for-`value` runs with the other --gather modes (config.exchange_legs_rows_per_s)")
     p.add_argument("--no-strict", action="store_true", help="skip the RO_PRECISION_F64 side measurement")
     p.add_argument("--no-large", action="store_true", help="skip the side measurements at the station configs' shapes (bins 524288, 65536)")
     p.add_argument("--soak-seconds", type=float, default=1.5,
-                   help="N = 1: behind the timed region, keep launching the same step for this long while the clock / "
+                   help="--full, N = 1: behind the timed region, keep launching the same step for this long while the clock / "
                         "power sampler runs (clock_power.soak): the package power the hwmon file reports is an average "
                         "over about a second, longer than the timed region of the default run (0 = skip)")
     p.add_argument("--pmc-traffic", type=float, default=None,
                    help="HBM bytes per launch from a separate rocprofv3 --pmc run (default: profiles/*_traffic.json)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="behind the timed steps, also run the side measurements and checks (parity, post-hoc kernel "
+                        "timing, clock / power soak, RO_PRECISION_F64 and station-shape legs, streaming, CPU baselines, "
+                        "other exchange legs, result hashes); a plain run does only what `value` needs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, a fixed seeded "
+                        "sample of rows where the whole would exceed the budget; at most 56 MiB in all)")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
 
 
 def make_bands(ro):
@@ -126,6 +142,27 @@ def synth_iq(torch, samples, seed, device):
     iq[:, 1] += (30.0 * torch.sin(ph)).to(torch.float32)
     del t, period_num, ph
     return iq
+
+
+# --dump-outputs: bytes per array on disk (56 MiB in all at most)
+DUMP_BUDGET = {"rows": 32 << 20, "scan_records": 4 << 20, "band": 16 << 20, "stitched_scan_records": 4 << 20}
+
+
+def sample_rows(torch, t, max_bytes, itemsize, seed=0xD0):
+    """rows of the 2-D device tensor t on the host: all of them if they fit in max_bytes at itemsize bytes per value,
+    else a fixed, seeded, sorted sample (the same rows for the same shape on every run)"""
+    n = t.shape[0]
+    k = max(1, min(n, max_bytes // (t.shape[1] * itemsize)))
+    if k == n:
+        return t.cpu().numpy()
+    idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    return t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+
+
+def records_f64(ro, recs):
+    """[n, 3] host array of 4-byte words holding ro_scan_record_t (noise, peak bin, average) -> float64 [n, 3], exact"""
+    r = np.ascontiguousarray(recs).view(ro.capi.SCAN_DTYPE).reshape(-1)
+    return np.stack([r["noise"], r["peak"], r["average"]], axis=1).astype(np.float64)
 
 
 def oracle_module(lib_path=None):
@@ -627,7 +664,7 @@ def main():
     # Whatever needs a compiler or a child process happens BEFORE this process touches the GPU (a fork + exec from a
     # process that holds a device is a hazard on this pool): the -O0 twin of the oracle for the cpu_baseline_O0 leg.
     o0_lib, o0_err = os.path.join(ROOT, "oracle", "libro_oracle_O0.so"), None
-    if world == 1 and not a.no_cpu_baseline and not os.path.exists(o0_lib):
+    if a.full and world == 1 and not a.no_cpu_baseline and not os.path.exists(o0_lib):
         try:
             subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "libro_oracle_O0.so"],
                                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
@@ -802,11 +839,20 @@ def main():
         mode["now"] = keep
         return ok > 0.5
 
+    def delivered(b):
+        """what step buffer b hands its caller besides this rank's rows and records: the band tile (stitched in row order
+        over the ranks when the step ends with an exchange) and the stitched records; None where there is none"""
+        if exchanging and mode["now"] != "none":
+            if (a.exchange == "capi" and mode["now"] == "root") or mode["now"] == "direct":
+                return g_tiles[b][:R_total], g_recs[b][:R_total]          # rows already in place
+            return sh.stitch(g_tiles[b], R_total, world), sh.stitch(g_recs[b], R_total, world)
+        return (tiles[b] if tile else None), None
+
     # the way a step ends is chosen ONCE, before anything is timed, and by all ranks together
     if exchanging and mode["now"] in ("root", "direct") and not usable(mode["now"]):
         mode["now"] = "all"
         mode["note"] = (mode["note"] or "") + ": all-gather instead"
-    sampler = ClockPowerSampler(torch, local_rank) if rank == 0 else None
+    sampler = ClockPowerSampler(torch, local_rank) if rank == 0 and a.full else None
     if sampler:
         sampler.start()
     for i in range(a.prewarm + a.warmup):
@@ -826,6 +872,23 @@ def main():
     if sampler:
         sampler.resume()
     t_bracket1 = time.perf_counter()
+    last = (a.steps - 1) & 1
+    if a.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, on the host before anything else runs on the device (the records
+        # travel as int32 so that no float path sees the peak bins' bit patterns)
+        dump = {"rows": sample_rows(torch, rows, DUMP_BUDGET["rows"], 4),
+                "scan_records": records_f64(ro, sample_rows(torch, recs[last].view(torch.int32),
+                                                            DUMP_BUDGET["scan_records"], 8))}
+        band, stitched = delivered(last)
+        if band is not None:
+            dump["band"] = sample_rows(torch, band, DUMP_BUDGET["band"], 4)
+        if stitched is not None:
+            dump["stitched_scan_records"] = records_f64(ro, sample_rows(torch, stitched.view(torch.int32),
+                                                                        DUMP_BUDGET["stitched_scan_records"], 8))
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+        del dump
     clock_power = None
     if sampler:
         # ... and on, outside the timed region: what the package settles at under this kernel (the power reading is a
@@ -854,31 +917,21 @@ def main():
     # rank 0's own scan records of the last step: its input (seed 0xC3, or the first time chunk of the C5 stream) and
     # therefore its records are the same whatever the number of ranks -- an N-rank run's line can be checked against the
     # one-rank run's, bit for bit, without the C5 workload
-    rank0_hash = None
-    if rank == 0:
+    rank0_hash = c5_hash = None
+    if a.full and rank == 0:
         import hashlib
-        rank0_hash = hashlib.sha256(recs[(a.steps - 1) & 1].cpu().numpy().tobytes()).hexdigest()[:32]
-    c5_hash = None
-    if c5:
-        import hashlib
-        last = (a.steps - 1) & 1
-        if exchanging and mode["now"] != "none":
-            if (a.exchange == "capi" and mode["now"] == "root") or mode["now"] == "direct":
-                t_all, r_all = g_tiles[last][:R_total], g_recs[last][:R_total]          # rows already in place
-            else:
-                t_all, r_all = sh.stitch(g_tiles[last], R_total, world), sh.stitch(g_recs[last], R_total, world)
-        else:
-            t_all, r_all = tiles[last], recs[last]
-        if rank == 0 and (world == 1 or mode["now"] != "none"):
+        rank0_hash = hashlib.sha256(recs[last].cpu().numpy().tobytes()).hexdigest()[:32]
+        if c5 and (world == 1 or mode["now"] != "none"):
+            t_all, r_all = delivered(last)
             hh = hashlib.sha256()
             hh.update(t_all.cpu().numpy().tobytes())
-            hh.update(r_all.cpu().numpy().tobytes())
+            hh.update((recs[last] if r_all is None else r_all).cpu().numpy().tobytes())
             c5_hash = hh.hexdigest()[:32]
 
     # ---- N > 1, OUTSIDE the timed region of `value`: the same K steps with the other ways of ending a step, so that
     # one run separates compute from exchange (all-gather as north_star words it, gather to rank 0, compute only)
     legs = None
-    if world > 1 and a.gather != "none" and not a.no_legs:
+    if a.full and world > 1 and a.gather != "none" and not a.no_legs:
         main_mode = mode["now"]
         legs = {main_mode: R_total * a.steps / dt}
         for m in ("all", "direct", "root", "none"):
@@ -899,9 +952,10 @@ def main():
         mode["now"] = main_mode
 
     # ---- kernel durations with HIP events on the launch stream (same launches as the timed loop)
-    ms_all, k_stft, k_scan = st.time_resident(iq, ro.RO_IQ_F32, samples, 0, R, rows, max(a.steps, 5),
-                                              d_records=recs[0], stream=sptr)
-    torch.cuda.synchronize(dev)
+    if a.full:
+        ms_all, k_stft, k_scan = st.time_resident(iq, ro.RO_IQ_F32, samples, 0, R, rows, max(a.steps, 5),
+                                                  d_records=recs[0], stream=sptr)
+        torch.cuda.synchronize(dev)
 
     out = None
     if rank == 0:
@@ -913,15 +967,14 @@ def main():
         # The dominant kernel's average launch duration: HIP events on the launch stream around the K launches of the
         # TIMED region when a step is exactly that one kernel (bins = 32768: scan and tile are its epilogue); for the
         # plans with a separate scan kernel the transform's own share comes from the event pairs of
-        # ro_stft_time_resident, taken right behind the timed region.
-        kernel_ms = gpu_ms_per_step if fused else k_stft
-        achieved = ALG_BYTES_PER_ROW * R / (kernel_ms * 1e-3) / 1e9
+        # ro_stft_time_resident, taken right behind the timed region (--full only).
+        kernel_ms = gpu_ms_per_step if fused else (k_stft if a.full else None)
         out = {
             "metric": "FFT rows/sec (spectra/sec), N=32768 75% overlap, incl. per-row bolid scan",
             "value": value, "unit": "rows/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "prewarm": a.prewarm,
             "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong" if c5 else "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": a.full,
             "config": {"workload": ("C5: one synthetic IQ stream of %.0f s at 48 kHz (%d rows), FFT bins=%d, overlap=%d, "
                                     "noise + a chirp every 30 s, split over the ranks by time chunk" %
                                     (a.c5_seconds, R_total, BINS, OVERLAP)) if c5 else
@@ -950,30 +1003,35 @@ def main():
                          # what holds the kernel below that bound (profiles/r05_stft_c3_summary.txt, r04_ledgers.md): the
                          # package's power cap under 3 N log2 N packed FMAs per row, not HBM (traffic = 1.01 x algorithmic)
                          "limiter": "package power cap (VALU)" if BINS == 32768 else "see DESIGN.md 4",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          # the same bytes over the wall-clock step of the timed region (host gaps and exchange included)
                          "frac_step": ALG_BYTES_PER_ROW * R / (dt / a.steps) / 1e9 / HBM_PEAK_GBS,
-                         # ... and over the event pairs of a separate loop of launches behind the timed region
-                         "frac_posthoc": ALG_BYTES_PER_ROW * R / (k_stft * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "traffic": a.pmc_traffic if a.pmc_traffic is not None else pmc_traffic(R),
-                         "traffic_source": "--pmc-traffic" if a.pmc_traffic is not None else
-                                           "newest profiles/r*_traffic.json (rocprofv3 --pmc passes of this command; "
-                                           "counters cannot be read from inside the run)",
                          "kernel": ("stft32k_kernel" if BINS == 32768 else "stft_kernel<%d>" % BINS),
-                         "kernel_ms": kernel_ms,
-                         "kernel_ms_source": "HIP events on the launch stream around the %d launches of the timed region"
-                                             % a.steps if fused else "ro_stft_time_resident event pairs behind the timed region",
-                         "kernel_ms_posthoc": k_stft,
-                         "algorithmic_bytes_per_launch": ALG_BYTES_PER_ROW * R,
-                         "scan_kernel_ms": k_scan},
+                         "algorithmic_bytes_per_launch": ALG_BYTES_PER_ROW * R},
             "device": st.device_name,
-            # what the device ran at while it was timed ("make the line self-qualifying"): at the package's
-            # 1400 W cap the shader clock, not the kernel, differs between boxes
-            "clock_power": clock_power,
-            "gpu_ms_per_step_events": gpu_ms_per_step, "step_ms_back_to_back": float(np.mean(ms_all)),
-            "step_ms_median": float(np.median(ms_all)), "step_ms_min": float(np.min(ms_all)),
+            "gpu_ms_per_step_events": gpu_ms_per_step,
         }
+        if kernel_ms is not None:
+            achieved = ALG_BYTES_PER_ROW * R / (kernel_ms * 1e-3) / 1e9
+            out["roofline"].update({
+                "achieved": achieved, "frac": achieved / HBM_PEAK_GBS, "kernel_ms": kernel_ms,
+                "kernel_ms_source": "HIP events on the launch stream around the %d launches of the timed region"
+                                    % a.steps if fused else "ro_stft_time_resident event pairs behind the timed region"})
+        if a.full:
+            out["roofline"].update({
+                # ... and over the event pairs of a separate loop of launches behind the timed region
+                "frac_posthoc": ALG_BYTES_PER_ROW * R / (k_stft * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "traffic": a.pmc_traffic if a.pmc_traffic is not None else pmc_traffic(R),
+                "traffic_source": "--pmc-traffic" if a.pmc_traffic is not None else
+                                  "newest profiles/r*_traffic.json (rocprofv3 --pmc passes of this command; "
+                                  "counters cannot be read from inside the run)",
+                "kernel_ms_posthoc": k_stft, "scan_kernel_ms": k_scan})
+            out.update({
+                # what the device ran at while it was timed ("make the line self-qualifying"): at the
+                # package's 1400 W cap the shader clock, not the kernel, differs between boxes
+                "clock_power": clock_power,
+                "step_ms_back_to_back": float(np.mean(ms_all)), "step_ms_median": float(np.median(ms_all)),
+                "step_ms_min": float(np.min(ms_all))})
 
         # the steady state under the package's power cap: the same launches for --soak-seconds behind the timed region (the
         # driver's 20-step region ends before the package has reached its cap; this is what a long job runs at)
@@ -983,20 +1041,21 @@ def main():
             out["roofline"]["ms_per_step_at_power_cap"] = soak_ms
 
         # ---- device copy bandwidth for context (float32 copy of the row buffer)
-        c = torch.empty_like(rows)
-        torch.cuda.synchronize(dev)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            c.copy_(rows)
-        e1.record()
-        torch.cuda.synchronize(dev)
-        out["device_copy_GBs"] = 2 * rows.numel() * 4 * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        out["roofline"]["frac_of_device_copy"] = achieved / out["device_copy_GBs"]      # report both
-        del c
+        if a.full:
+            c = torch.empty_like(rows)
+            torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                c.copy_(rows)
+            e1.record()
+            torch.cuda.synchronize(dev)
+            out["device_copy_GBs"] = 2 * rows.numel() * 4 * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            out["roofline"]["frac_of_device_copy"] = achieved / out["device_copy_GBs"]      # report both
+            del c
 
         # ---- parity spot check of this run's output (oracle = checker only)
-        if not a.no_parity:
+        if a.full and not a.no_parity:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import ro_oracle as O
             pick = [0, 1, R // 2, R - 1]
@@ -1026,7 +1085,7 @@ def main():
 
         # ---- the strict-precision mode next to the headline (never the headline): the same input and rows per step, then
         # the C2 shape
-        if world == 1 and not a.no_strict:
+        if a.full and world == 1 and not a.no_strict:
             out["strict_precision"] = strict_leg(torch, ro, dev, local_rank, not a.no_parity, BINS, OVERLAP, R, FS, bands,
                                                  ro.RO_WINDOW_HANN if a.window == "hann" else ro.RO_WINDOW_NUTTALL,
                                                  max(a.steps, 20), iq=iq, rows_buf=rows, recs_buf=recs[1])
@@ -1039,7 +1098,7 @@ def main():
 
         # ---- the station configs' own shapes next to the headline (never the headline), inputs resident:
         # Ionozor.json:27-28 on the four-step pair of kernels, Bolidozor.json:45-46 on the one-kernel large form
-        if world == 1 and not a.no_large and not c5 and BINS == 32768:
+        if a.full and world == 1 and not a.no_large and not c5 and BINS == 32768:
             out["ionozor"] = large_leg(torch, ro, dev, local_rank, not a.no_parity, 524288, 262144, 1024, "Ionozor.json:27-28",
                                        "four_cols_kernel + four_rows_kernel + scan_kernel (csrc/ro_fourstep.hip)",
                                        "r05_traffic_524288.json")
@@ -1053,7 +1112,7 @@ def main():
         # ---- the drop-in path at full speed (never the headline): Frontend::process -> HipWaterfallBackend::process
         # with 4096-sample vector<Complex> calls (src/RawStream.cpp:44-66) -> kernels -> full rows back to the host row
         # ring -> BolidRecorder::update per row; PCIe both ways included, handle creation and warm-up calls excluded
-        if world == 1 and not a.no_streaming and not c5:
+        if a.full and world == 1 and not a.no_streaming and not c5:
             pcie = pcie_copy_rates(torch, dev)
             out["streaming"] = streaming_leg(a.stream_seconds, 0, pcie)
             # (the Backend's own default bounds a batch by latency -- one second of rows = 6; the same path with 256 rows
@@ -1064,7 +1123,7 @@ def main():
         # on libfftw3 itself (fftw_plan_dft_1d(..., FFTW_FORWARD, FFTW_ESTIMATE) + fftw_execute, the reference's call
         # sites: src/FFTBackend.cpp:117-120,236) when this host has libfftw3.so.3, else on a vendor FFT behind the same
         # fftw3 API (MKL's FFTW3 interface), else on the oracle's own radix-2 transform; `fft_engine` says which.
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             n_cpu = min(R, 32768 if BINS >= 16384 else 262144)
             host = iq[:BINS + HOP * (n_cpu - 1)].cpu().numpy()
             O = oracle_module()

@@ -12,7 +12,8 @@ def test_bench_flags():
                        timeout=120)
     assert r.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup", "--prewarm", "--gather", "--exchange", "--workload", "--c5-seconds",
-                 "--rows", "--bins", "--overlap", "--no-streaming", "--stream-seconds", "--pattern", "--no-large", "--no-strict"):
+                 "--rows", "--bins", "--overlap", "--no-streaming", "--stream-seconds", "--pattern", "--no-large", "--no-strict",
+                 "--full", "--dump-outputs"):
         assert flag in r.stdout, flag
     # the all-gather north_star names is what ends a step inside the timed region unless asked otherwise
     assert "all (default)" in " ".join(r.stdout.split())

@@ -35,7 +35,7 @@ def run_bench(argv):
 
 
 def test_bench_line_has_the_contract_fields(ro, torch_cuda):
-    d = run_bench(["--steps", "4", "--warmup", "1", "--prewarm", "2", "--rows", "4096", "--cpu-seconds", "1.5",
+    d = run_bench(["--full", "--steps", "4", "--warmup", "1", "--prewarm", "2", "--rows", "4096", "--cpu-seconds", "1.5",
                    "--stream-seconds", "0.4"])
     assert d["unit"] == "rows/s" and d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["prewarm"] == 2
     assert d["dtype"] == "f32" and d["vs_baseline"] is None and d["scaling"] == "weak"
@@ -73,11 +73,53 @@ def test_bench_line_has_the_contract_fields(ro, torch_cuda):
     assert "cpu_baseline_O0" in d and "error" not in d["cpu_baseline_O0"]
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_what_they_computed(ro, oracle, torch_cuda, tmp_path):
+    """a plain run (no --full) is the timed steps and the line; --dump-outputs writes the last step's rows (a fixed
+    sample) and scan records, the same from run to run, and they are what the oracle computes from the bench's input"""
+    torch = torch_cuda
+    R, bins, overlap = 1024, 32768, 24576
+    lines = []
+    for k in range(2):
+        lines.append(run_bench(["--steps", "3", "--warmup", "1", "--prewarm", "1", "--rows", str(R),
+                                "--dump-outputs", str(tmp_path / str(k))]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["full"] is False and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["unit"] == "rows/s" and "N=32768" in d["metric"]
+    assert d["value"] * d["ms_per_step"] * 1e-3 == pytest.approx(R)            # R rows in one timed step
+    assert d["roofline"]["frac"] == pytest.approx(d["roofline"]["achieved"] / 8000.0)
+    for k in ("parity", "strict_precision", "ionozor", "bolidozor", "streaming", "cpu_baseline", "clock_power",
+              "device_copy_GBs", "step_ms_back_to_back"):
+        assert k not in d, k
+    files = sorted(os.listdir(tmp_path / "0"))
+    assert files == ["rows.npy", "scan_records.npy"] and sorted(os.listdir(tmp_path / "1")) == files
+    assert sum(os.path.getsize(tmp_path / "0" / f) for f in files) <= 64e6
+    got = {f: np.load(tmp_path / "0" / f) for f in files}
+    for f in files:
+        assert np.array_equal(got[f], np.load(tmp_path / "1" / f), equal_nan=True), f
+    rows, recs = got["rows.npy"], got["scan_records.npy"]
+    assert rows.dtype == np.float32 and rows.shape == (256, bins)               # 32 MiB of the 128 MiB of rows
+    assert recs.dtype == np.float64 and recs.shape == (R, 3)
+    # the sample's rows are the seeded choice of bench.sample_rows; two of them against the oracle on the bench's input
+    sys.path.insert(0, ROOT)
+    import bench
+    idx = np.sort(np.random.default_rng(0xD0).choice(R, 256, replace=False))
+    hop = bins - overlap
+    iq = bench.synth_iq(torch, bins + hop * (R - 1), 0xC3, "cuda")
+    bands = bench.make_bands(ro)
+    for j in (0, 255):
+        r = int(idx[j])
+        want = oracle.stft(iq[r * hop:r * hop + bins].cpu().numpy(), bins, overlap)[0]
+        assert np.abs(rows[j].astype(np.float64) - want).max() / want.max() <= 1e-5
+        n, p, av = oracle.scan_rows(rows[j][None, :], bands.low_noise, bands.noise_width, bands.low_detect,
+                                    bands.detect_width, bands.avg_bins)
+        assert (n[0], p[0], av[0]) == tuple(recs[r]), r
+
+
 @pytest.mark.parametrize("exchange,pattern", [("torch", "nccl"), ("capi", "nccl"), ("capi", "direct")])
 def test_bench_c5_hash_is_the_hash_of_the_stream(ro, torch_cuda, exchange, pattern):
     torch = torch_cuda
     seconds = 900.0
-    d = run_bench(["--workload", "c5", "--c5-seconds", str(seconds), "--exchange", exchange, "--pattern", pattern, "--steps", "2", "--warmup", "1",
+    d = run_bench(["--full", "--workload", "c5", "--c5-seconds", str(seconds), "--exchange", exchange, "--pattern", pattern, "--steps", "2", "--warmup", "1",
                    "--prewarm", "1", "--no-cpu-baseline", "--no-strict", "--no-parity", "--no-streaming"])
     assert d["scaling"] == "strong"
     got = d["config"]["c5_hash_of_stitched_band_and_records"]

@@ -12,7 +12,7 @@ def counters(sub):
             acc[row["Kernel_Name"]][row["Counter_Name"]].append(float(row["Counter_Value"]))
     return acc
 
-print("== kernel-trace stats (rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-parity)")
+print("== kernel-trace stats (rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-parity)")
 for f in glob.glob(os.path.join(d, "trace", "*", "*_kernel_stats.csv")):
     for row in csv.DictReader(open(f)):
         if "ro::" in row["Name"]:

@@ -4,7 +4,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 smi() { rocm-smi --showpower --showclocks --showtemp 2>/dev/null | grep -E "Power|sclk|mclk|fclk|junction" | tr -s ' ' | tr '\n' ';'; echo; }
 echo "idle before: $(smi)"
-python3 $ROOT/bench.py $POWER_ARGS --steps ${POWER_STEPS:-12000} --warmup 5 --prewarm 5 --no-cpu-baseline --no-strict --no-streaming --no-parity > /tmp/power_bench.json 2>/dev/null &
+python3 $ROOT/bench.py --full $POWER_ARGS --steps ${POWER_STEPS:-12000} --warmup 5 --prewarm 5 --no-cpu-baseline --no-strict --no-streaming --no-parity > /tmp/power_bench.json 2>/dev/null &
 BP=$!
 sleep 4
 for i in 1 2 3 4 5 6; do echo "under load $i: $(smi)"; sleep 1; done
