@@ -57,7 +57,8 @@ enum { RO_IQ_F32 = 0, RO_IQ_I16 = 1, RO_IQ_F64 = 2 };
  *       narrowing to the float row (src/FFTBackend.cpp:117-120,229-236, src/WaterfallBackend.cpp:492-505).  Bins
  *       256 ... 65536 keep the complex-double row in a compute unit's registers (samples read once, row written
  *       once; below 4096 bins 2 ... 16 rows share a workgroup); 131072 ... 1048576 are passes through HBM scratch.  Rows within 1e-5 of the reference PER BIN
- *       (measured <= 1.2e-7: one float32 ulp, at 60 dB of dynamic range); 2.5 times slower than F32 at 32768 bins.
+ *       (measured <= 1.2e-7: one float32 ulp, at 60 dB of dynamic range); about 2.1 times slower than F32 at 32768 bins
+ *       (0.203 against 0.430 of the HBM peak: profiles/r06_bench_line_final.json).
  *       Complex spectra (ro_stft_spectra_resident) up to 65536 bins.
  *  (Value 2 was ABI 4's RO_PRECISION_F64_ONE_LAUNCH, an experiment that measured slower; ro_stft_create answers
  *  RO_ERR_UNSUPPORTED for it.) */

@@ -977,7 +977,9 @@ __global__ __launch_bounds__((1 << LOGM) / 16, 4) void f64r_kernel(Args a)
     }
 }
 
-template <int LOGM, int D, int FMT, int LOGB = 0> static hipError_t launch_one(const Args &a, hipStream_t s)
+// the per-device attributes of a plan's (non-spectra) kernels, set on first use; `cus` = the device's CU count.  Also
+// called on its own (f64reg_prepare) before a launch is captured into a graph: no attribute call then reaches the capture.
+template <int LOGM, int D, int FMT, int LOGB = 0> static hipError_t prepare_one(int &cus)
 {
     using G = Geo<LOGM>;
     static std::mutex lock;
@@ -987,19 +989,27 @@ template <int LOGM, int D, int FMT, int LOGB = 0> static hipError_t launch_one(c
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    int cus;
-    {
-        std::lock_guard<std::mutex> g(lock);
-        if (!ready[dev]) {
-            const void *fn[2] = {reinterpret_cast<const void *>(&f64r_kernel<LOGM, D, FMT, false, LOGB>),
-                                 reinterpret_cast<const void *>(&f64r_kernel<LOGM, D, FMT, true, LOGB>)};
-            for (int i = 0; i < 2; ++i)
-                if ((e = hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES)) != hipSuccess) return e;
-            if ((e = hipDeviceGetAttribute(&cus_of[dev], hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-            ready[dev] = true;
-        }
-        cus = cus_of[dev];
+    std::lock_guard<std::mutex> g(lock);
+    if (!ready[dev]) {
+        const void *fn[2] = {reinterpret_cast<const void *>(&f64r_kernel<LOGM, D, FMT, false, LOGB>),
+                             reinterpret_cast<const void *>(&f64r_kernel<LOGM, D, FMT, true, LOGB>)};
+        for (int i = 0; i < 2; ++i)
+            if ((e = hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES)) != hipSuccess) return e;
+        if ((e = hipDeviceGetAttribute(&cus_of[dev], hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+        ready[dev] = true;
     }
+    cus = cus_of[dev];
+    return hipSuccess;
+}
+
+template <int LOGM, int D, int FMT, int LOGB = 0> static hipError_t launch_one(const Args &a, hipStream_t s)
+{
+    using G = Geo<LOGM>;
+    int cus = 0;
+    hipError_t e = prepare_one<LOGM, D, FMT, LOGB>(cus);
+    if (e != hipSuccess) return e;
+    int dev = 0;
+    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
     // persistent grid: 1024 / T workgroups per CU, per XCD a multiple of D, never more than the XCD's share of sub-rows
     const int64_t per_xcd = (((a.rows + (1 << LOGB) - 1) >> LOGB) + 7) / 8;      // (LOGB > 0: tiles of 2^LOGB rows)
     int64_t slots = (int64_t)(cus / 8) * (1024 / G::T);
@@ -1025,14 +1035,21 @@ template <int LOGM, int D, int FMT, int LOGB = 0> static hipError_t launch_one(c
     return hipGetLastError();
 }
 
-template <int FMT> static hipError_t launch_fmt(int m_log2, int dec, int logb, const Args &a, hipStream_t s)
+// PREP: only the attributes of the plan's kernels (prepare_one), nothing launched
+template <int LOGM, int D, int FMT, int LOGB, bool PREP> static hipError_t run_one(const Args &a, hipStream_t s)
+{
+    int cus = 0;
+    return PREP ? prepare_one<LOGM, D, FMT, LOGB>(cus) : launch_one<LOGM, D, FMT, LOGB>(a, s);
+}
+
+template <int FMT, bool PREP = false> static hipError_t launch_fmt(int m_log2, int dec, int logb, const Args &a, hipStream_t s)
 {
 #define RO_F64R_CASE(LM, DD) \
-    if (m_log2 == LM && dec == DD) return launch_one<LM, DD, FMT>(a, s)
-    if (logb == 1) return launch_one<12, 1, FMT, 1>(a, s);
-    if (logb == 2) return launch_one<12, 1, FMT, 2>(a, s);
-    if (logb == 3) return launch_one<12, 1, FMT, 3>(a, s);
-    if (logb == 4) return launch_one<12, 1, FMT, 4>(a, s);
+    if (m_log2 == LM && dec == DD) return run_one<LM, DD, FMT, 0, PREP>(a, s)
+    if (logb == 1) return run_one<12, 1, FMT, 1, PREP>(a, s);
+    if (logb == 2) return run_one<12, 1, FMT, 2, PREP>(a, s);
+    if (logb == 3) return run_one<12, 1, FMT, 3, PREP>(a, s);
+    if (logb == 4) return run_one<12, 1, FMT, 4, PREP>(a, s);
     RO_F64R_CASE(12, 1);
     RO_F64R_CASE(13, 1);
     RO_F64R_CASE(14, 1);
@@ -1118,6 +1135,17 @@ void f64reg_tables(int bins, const float *window, F64RegTables &t)
                     o[1] = f64r::wexp((long double)((2 * e) % bins), (long double)bins);
                 }
     }
+}
+
+hipError_t f64reg_prepare(int bins, int fmt)
+{
+    int m_log2 = 0, dec = 0, logb = 0;
+    if (!f64r::plan(bins, m_log2, dec, logb)) return hipErrorInvalidValue;
+    const f64r::Args none{};
+    if (fmt == RO_FMT_F32) return f64r::launch_fmt<RO_FMT_F32, true>(m_log2, dec, logb, none, nullptr);
+    if (fmt == RO_FMT_I16) return f64r::launch_fmt<RO_FMT_I16, true>(m_log2, dec, logb, none, nullptr);
+    if (fmt == RO_IQ_F64) return f64r::launch_fmt<RO_IQ_F64, true>(m_log2, dec, logb, none, nullptr);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_f64reg(int bins, int fmt, const F64RegArgs &a, hipStream_t s)

@@ -121,6 +121,7 @@ struct F64RegArgs {
 bool       f64reg_supported(int bins);           // 256 ... 65536
 void       f64reg_tables(int bins, const float *window, F64RegTables &t);
 hipError_t launch_f64reg(int bins, int fmt, const F64RegArgs &a, hipStream_t s);
+hipError_t f64reg_prepare(int bins, int fmt);    // the plan's one-time kernel attributes, nothing launched (ahead of a capture)
 
 #ifdef RO_DIAG
 // (diagnostic builds only: round 5's experiment, not in the product library)

@@ -153,15 +153,20 @@ int run_stream_batch(ro_stft *h, int64_t rows)
     // the sink's slots: seven calls.  The slots' streams overlap a batch with the one or two before it; a slot's
     // own batches are ordered by its stream.  Partial batches (a flush) and the first batch of a slot take the plain path.
     const bool small = (size_t)h->batch_rows * h->out_cols * sizeof(float) <= ((size_t)4 << 20);
-    // (float32 power-of-two single-kernel handles only: the FP64 and chirp-z paths keep per-launch host state -- scratch
-    // blocks, an inner handle -- that a replayed graph would not see, and the four-step sizes hand Z from their column
-    // kernel to their row kernel through ONE scratch block per handle, which two slots' graphs on two streams would share)
-    bool graphed = RO_STREAM_GRAPH && small && h->sink && !h->cfg.tile_ln && !h->f64 && !h->czt && !h->four &&
+    // (power-of-two single-kernel handles only, float32 or the FP64 register kernel (256 ... 65536 bins): the FP64 passes
+    // through HBM scratch and the chirp-z path keep per-launch host state -- scratch blocks, an inner handle -- that a
+    // replayed graph would not see, and the four-step sizes hand Z from their column kernel to their row kernel through ONE
+    // scratch block per handle, which two slots' graphs on two streams would share.  The register kernel reads its tables
+    // and writes its rows and nothing else; its grid is a function of `rows`, which is batch_rows for every graphed batch.)
+    bool graphed = RO_STREAM_GRAPH && small && h->sink && !h->cfg.tile_ln && (!h->f64 || h->f64reg) && !h->czt && !h->four &&
                    rows == h->batch_rows && sl.uses > 0;
     ro_scan_record_t *g_recs = h->cfg.enable_scan ? sl.d_records : nullptr;
     if (graphed && (!sl.gexec || sl.graph_fmt != h->stage_fmt)) {
         if (sl.gexec) { (void)hipGraphExecDestroy(sl.gexec); sl.gexec = nullptr; }
         if (!sl.gstream) step(hipStreamCreateWithFlags(&sl.gstream, hipStreamNonBlocking), "hipStreamCreateWithFlags");
+        // the register kernel sets its attributes on its first launch in a format: done here, outside the capture (a
+        // stream that widened its staging to doubles captures a format no plain batch has launched yet)
+        if (h->f64reg) step(ro::f64reg_prepare(h->bins, h->stage_fmt), "f64reg_prepare");
         hipGraph_t g = nullptr;
         if (rc == RO_OK && step(hipStreamBeginCapture(sl.gstream, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture")) {
             step(hipMemcpyAsync(sl.d_iq, sl.h_in, (size_t)need * sb, hipMemcpyHostToDevice, sl.gstream), "upload");

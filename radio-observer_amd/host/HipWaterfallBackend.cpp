@@ -7,8 +7,11 @@
 #include <sys/time.h>
 
 #include <algorithm>
+#include <cerrno>
+#include <climits>
 #include <cstdio>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 namespace ro {
@@ -119,6 +122,64 @@ void WaterfallBase::processRow(const float *row, const ro_scan_record_t *scan, D
     for (Recorder *r : recorders_) r->update();                                  // :534-536
 }
 
+bool parseWaterfallKeys(const std::map<std::string, std::string> &keys, WaterfallConfig *cfg, std::string *err)
+{
+    WaterfallConfig c = *cfg;
+    std::string why;
+    auto asInt = [&](const char *key, int *out) {
+        auto it = keys.find(key);
+        if (it == keys.end()) return true;
+        const char *s = it->second.c_str();
+        char *end = nullptr;
+        errno = 0;
+        const long v = std::strtol(s, &end, 10);
+        if (end == s || *end != '\0' || errno != 0 || v < INT_MIN || v > INT_MAX) {
+            why = std::string("waterfall: \"") + key + "\" must be an integer, got \"" + it->second + "\"";
+            return false;
+        }
+        *out = (int)v;
+        return true;
+    };
+    auto asDouble = [&](const char *key, double *out) {
+        auto it = keys.find(key);
+        if (it == keys.end()) return true;
+        const char *s = it->second.c_str();
+        char *end = nullptr;
+        errno = 0;
+        const double v = std::strtod(s, &end);
+        if (end == s || *end != '\0' || errno != 0) {
+            why = std::string("waterfall: \"") + key + "\" must be a number, got \"" + it->second + "\"";
+            return false;
+        }
+        *out = v;
+        return true;
+    };
+    auto asString = [&](const char *key, std::string *out) {
+        auto it = keys.find(key);
+        if (it != keys.end()) *out = it->second;
+    };
+    bool ok = asInt("bins", &c.bins) && asInt("overlap", &c.overlap) && asInt("buffer_chunk_size", &c.buffer_chunk_size) &&
+              asDouble("iq_gain", &c.iq_gain) && asInt("iq_phase_shift", &c.iq_phase_shift);
+    asString("origin", &c.origin);
+    asString("metadata_path", &c.metadata_path);
+    auto it = keys.find("precision");
+    if (ok && it != keys.end()) {
+        if (it->second == "f32") c.precision = RO_PRECISION_F32;
+        else if (it->second == "f64") c.precision = RO_PRECISION_F64;
+        else {
+            why = "waterfall: unknown \"precision\" \"" + it->second + "\" (expected \"f32\" or \"f64\")";
+            ok = false;
+        }
+    }
+    if (!ok) {
+        if (err) *err = why;
+        return false;
+    }
+    *cfg = c;
+    if (err) err->clear();
+    return true;
+}
+
 HipWaterfallBackend::HipWaterfallBackend(const WaterfallConfig &cfg) : WaterfallBase(cfg)
 {
     buffer_.setStorage(pinnedAlloc, pinnedFree, &cfg_.device);       // (without a device: nullptr, i.e. the heap)
@@ -150,6 +211,9 @@ void HipWaterfallBackend::startStream(StreamInfo info)
     c.iq_gain = cfg_.iq_gain;
     c.iq_phase_shift = cfg_.iq_phase_shift;
     c.device = cfg_.device;
+    // (FP64 at a length the library has no double plan for -- a chirp-z length -- is refused by ro_stft_create below:
+    // lastError() carries its text and no rows come; there is no quiet float32 instead)
+    c.precision = cfg_.precision;
     // Rows reach Recorder::update() a batch late (the GPU wants more than one row per launch; recorders only look
     // backwards).  The library's own default batch is sized for throughput (~64 MiB of rows: 87 s of stream at
     // N = 32768 / 75 %); behind the Backend interface the default is bounded by LATENCY instead: at most one second

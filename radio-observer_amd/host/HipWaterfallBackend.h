@@ -10,6 +10,7 @@
 #pragma once
 
 #include <deque>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -80,7 +81,18 @@ struct WaterfallConfig {
     int         device = 0;
     int         max_batch_rows = 0;          // rows per kernel launch; small = low latency
     bool        keep_raw = true;             // keep the raw I/Q ring (the reference always does: FFTBackend.cpp:217-223)
+    // arithmetic of the rows: RO_PRECISION_F32 (float32 butterflies, rows within 1e-5 of the row maximum) or
+    // RO_PRECISION_F64 (the reference's double arithmetic, src/FFTBackend.cpp:117-120,229-236: every bin within one
+    // float32 ulp; 256 ... 65536 bins take the doubles of struct Complex un-narrowed).  The raw I/Q ring holds float
+    // pairs in both modes (src/FFTBackend.cpp:217-223).
+    int         precision = RO_PRECISION_F32;
 };
+
+// The "waterfall" factory's keys (WaterfallBackend::make, src/WaterfallBackend.cpp:620-646): bins, overlap, origin,
+// metadata_path, buffer_chunk_size, iq_gain, iq_phase_shift -- plus "precision": "f32" | "f64".  Keys absent from
+// `keys` keep *cfg's values; other keys are ignored, as the reference ignores them.  A value that does not parse (a
+// number with trailing text, an unknown precision) is refused: false, *cfg untouched, the reason in *err.
+bool parseWaterfallKeys(const std::map<std::string, std::string> &keys, WaterfallConfig *cfg, std::string *err);
 
 // Everything WaterfallBackend is to its recorders (src/WaterfallBackend.h:239-290 and the FFTBackend
 // accessors they call, src/FFTBackend.h:110-200): the row ring, the raw handles, the bin/Hz/time
