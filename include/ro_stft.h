@@ -278,6 +278,36 @@ int ro_stft_ln_tile_resident(ro_stft_t *h, const float *d_rows, int64_t row_stri
                              int first_col, int cols, float *d_ln, uint8_t *d_u8, float *d_minmax,
                              void *stream);
 
+/* ---- band-only transform ----------------------------------------------------
+ * Nobody downstream reads a row whole: the snapshot recorder keeps the columns low_freq ... hi_freq of each row
+ * (src/WaterfallBackend.cpp:174-205) and BolidRecorder::update reads the noise band, the detect band and the
+ * average's window around the peak (src/BolidRecorder.cpp:121-132).  These three calls serve exactly that. */
+/* 1 if ro_stft_band_resident can produce `cols` columns of a `bins`-bin row: bins a power of two
+ * 16384 ... 1048576, 1 <= cols <= 1024.  Pure host. */
+int ro_stft_band_supported(int bins, int cols);
+
+/* Smallest column range that holds everything the recorders read of a row: the noise band (noise(),
+ * src/BolidRecorder.cpp:313-317), the detect band (peak(), :323-335) widened by what average() reads around any peak
+ * (:126-132, :338-347: [low_detect - avg_bins/2, low_detect + detect_width - 1 - avg_bins/2 + avg_bins)), and, if
+ * tile_cols > 0, the tile (the snapshot's column cut, src/WaterfallBackend.cpp:176,204).
+ * RO_ERR_INVALID if that range leaves [0, bins).  Pure host. */
+int ro_bands_hull(const ro_bands_t *bands, int bins, int tile_first_col, int tile_cols,
+                  int *first_col, int *cols);
+
+/* Columns [first_col, first_col + cols) of rows [first_row, +rows), and nothing else: no full row is
+ * computed or written (the columns the snapshot cut of src/WaterfallBackend.cpp:176,204 keeps, or the three reads of
+ * BolidRecorder::update, src/BolidRecorder.cpp:121-132).  d_band: device, rows x band_stride floats (band_stride >=
+ * cols; floats beyond cols in a row are not touched).  d_records (optional; needs enable_scan and the handle's bands,
+ * with the average's margin, inside the band -- RO_ERR_INVALID otherwise): the same records
+ * ro_stft_scan_resident gives on the full row.  RO_PRECISION_F32 handles, RO_IQ_F32 / RO_IQ_I16;
+ * RO_ERR_UNSUPPORTED for FP64 handles, chirp-z lengths and shapes ro_stft_band_supported refuses.
+ * Same float32 bar as the rows: within 1e-5 of the FULL row's maximum.  Two launches on the same input give the same
+ * bits.  Asynchronous on `stream`; uses handle scratch, so one launch of a handle in flight at a time. */
+int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples,
+                          int64_t first_row, int64_t rows, int first_col, int cols,
+                          float *d_band, int64_t band_stride,
+                          ro_scan_record_t *d_records, void *stream);
+
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel
  * when records are requested).  kernel_ms_out (optional, 2 floats) receives the

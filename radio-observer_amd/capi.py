@@ -106,6 +106,10 @@ _EXPORTS = {
                                         C.c_void_p]),
     "ro_stft_ln_tile_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ro_stft_band_supported": (C.c_int, [C.c_int, C.c_int]),
+    "ro_bands_hull": (C.c_int, [C.POINTER(Bands), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ro_stft_band_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -290,6 +294,18 @@ def bins_supported(bins):
     return bool(library().ro_bins_supported(bins))
 
 
+def band_supported(bins, cols):
+    """whether Stft.band_resident can produce `cols` columns of a `bins`-bin row -- ro_stft_band_supported"""
+    return bool(library().ro_stft_band_supported(bins, cols))
+
+
+def bands_hull(bands, bins, tile_first_col=0, tile_cols=0):
+    """(first_col, cols) of the smallest column range that holds everything the recorders read -- ro_bands_hull"""
+    first, cols = C.c_int(), C.c_int()
+    _check(library().ro_bands_hull(C.byref(bands), bins, tile_first_col, tile_cols, C.byref(first), C.byref(cols)))
+    return first.value, cols.value
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -411,6 +427,12 @@ class Stft:
         """complex spectra (rows x stride x {re, im} float32, bin k at element k) instead of magnitudes"""
         _check(library().ro_stft_spectra_resident(self._h, _ptr(d_iq), fmt, samples, first_row, rows,
                                                   _ptr(d_spectra), stride or self.bins, _ptr(stream)))
+
+    def band_resident(self, d_iq, fmt, samples, first_row, rows, first_col, cols, d_band, band_stride=None,
+                      d_records=None, stream=None):
+        """columns [first_col, +cols) of the rows and nothing else (rows x band_stride float32), plus their scan records"""
+        _check(library().ro_stft_band_resident(self._h, _ptr(d_iq), fmt, samples, first_row, rows, first_col, cols,
+                                               _ptr(d_band), band_stride or cols, _ptr(d_records), _ptr(stream)))
 
     def scan_resident(self, d_rows, rows, d_records, row_stride=None, stream=None):
         _check(library().ro_stft_scan_resident(self._h, _ptr(d_rows), row_stride or self.bins, rows,

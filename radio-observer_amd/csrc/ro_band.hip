@@ -1,0 +1,222 @@
+// ro_band.hip -- the band-only transform (gfx950): at most 1024 consecutive columns of the fft-shifted row, computed
+// from the samples without the full-size transform and without a full row in HBM.  ro_band.h has the arithmetic.
+//
+//   band_slab_kernel<M, A, FMT>   one workgroup = one row x one slab of A residues a: loads its A x M samples (gain and
+//                                 window applied while loading, like the first pass of the float32 row kernels), runs
+//                                 the A transforms of M points in place in LDS (radix-4 decimation in frequency, a last
+//                                 radix-2 level at M = 512; results in digit-reversed cells), and writes the slab's
+//                                 twiddled partial sum of every wanted column to scratch
+//   band_finish_kernel            adds a row's partials in slab order, takes the magnitude, stores the band row
+//
+// LDS image: cell (b, t) at b A + t, float2 -- the A residues of one b are one 128-byte (A = 16) or 64-byte (A = 8) run,
+// in LDS as in the stream, so a wave's butterfly reads and writes are runs of 64 consecutive cells until the last
+// radix-4 level (blocks of 4 cells per residue: two-way conflicts there, one level in five).
+// No atomics anywhere: the order of every sum is fixed by the index maps, two launches give the same bits.
+#include "ro_band.h"
+#include "ro_kernels.h"
+
+namespace ro {
+
+namespace {
+
+typedef float c2f __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ c2f band_cmul(c2f a, c2f w)
+{
+    return (c2f){a.x * w.x - a.y * w.y, a.y * w.x + a.x * w.y};
+}
+
+template <int FMT> struct BandSample;
+template <> struct BandSample<RO_FMT_F32> {
+    static constexpr int BYTES = 8;                     // rows start at any sample: 8-byte alignment is all there is
+    static __device__ __forceinline__ c2f load(const char *row, int n)
+    {
+        const float2 x = reinterpret_cast<const float2 *>(row)[n];
+        return (c2f){x.x, x.y};
+    }
+};
+template <> struct BandSample<RO_FMT_I16> {
+    static constexpr int BYTES = 4;
+    static __device__ __forceinline__ c2f load(const char *row, int n)
+    {
+        const unsigned u = reinterpret_cast<const unsigned *>(row)[n];
+        return (c2f){(float)(short)(u & 0xffffu), (float)(short)(u >> 16)};
+    }
+};
+
+// cell index b of result r of an M-point transform after the in-place levels (radix 4 while the span allows, then 2):
+// the level of span S sends result digit r mod R to sub-block (r mod R) S / R
+template <int M> __host__ __device__ constexpr int band_pos(int r)
+{
+    int pos = 0;
+    for (int s = M; s > 1;) {
+        const int radix = s >= 4 ? 4 : 2;
+        pos += (r % radix) * (s / radix);
+        r /= radix;
+        s /= radix;
+    }
+    return pos;
+}
+
+// one radix-4 level of span S of all A transforms, in place; T threads, A M / 4 butterflies
+template <int M, int A, int S> __device__ __forceinline__ void band_radix4(c2f *cell, const float2 *__restrict__ tw, int tid)
+{
+    constexpr int Q = S / 4, T = A * M / 16;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int w = tid + T * i;                     // < A M / 4
+        const int t = w % A, u = w / A;                // u < M / 4
+        const int j = u % Q, base = (u / Q) * S + j;   // base + 3 Q < M
+        c2f *p = cell + base * A + t;
+        const c2f x0 = p[0], x1 = p[Q * A], x2 = p[2 * Q * A], x3 = p[3 * Q * A];
+        const c2f s02 = x0 + x2, d02 = x0 - x2, s13 = x1 + x3, d13 = x1 - x3;
+        const c2f md = (c2f){d13.y, -d13.x};           // -i (x1 - x3)
+        c2f y0 = s02 + s13, y1 = d02 + md, y2 = s02 - s13, y3 = d02 - md;
+        if constexpr (Q > 1) {
+            constexpr int STEP = M / S;                // exp(-2 pi i q j / S) = tw[q j STEP], q j STEP < 3 M / 4
+            const float2 w1 = tw[j * STEP], w2 = tw[2 * j * STEP], w3 = tw[3 * j * STEP];
+            y1 = band_cmul(y1, (c2f){w1.x, w1.y});
+            y2 = band_cmul(y2, (c2f){w2.x, w2.y});
+            y3 = band_cmul(y3, (c2f){w3.x, w3.y});
+        }
+        p[0] = y0;
+        p[Q * A] = y1;
+        p[2 * Q * A] = y2;
+        p[3 * Q * A] = y3;
+    }
+}
+
+// the last level of M = 512: pairs of neighbouring cells, no twiddle
+template <int M, int A> __device__ __forceinline__ void band_radix2_last(c2f *cell, int tid)
+{
+    constexpr int T = A * M / 16;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int w = tid + T * i;                     // < A M / 2
+        const int t = w % A, u = w / A;
+        c2f *p = cell + 2 * u * A + t;
+        const c2f x0 = p[0], x1 = p[A];
+        p[0] = x0 + x1;
+        p[A] = x0 - x1;
+    }
+}
+
+template <int M, int A, int S> __device__ __forceinline__ void band_levels(c2f *cell, const float2 *__restrict__ tw, int tid)
+{
+    if constexpr (S >= 4) {
+        band_radix4<M, A, S>(cell, tw, tid);
+        __syncthreads();
+        band_levels<M, A, S / 4>(cell, tw, tid);
+    } else if constexpr (S == 2) {
+        band_radix2_last<M, A>(cell, tid);
+        __syncthreads();
+    }
+}
+
+template <int M, int A, int FMT>
+__global__ __launch_bounds__(A * M / 16) void band_slab_kernel(BandArgs a)
+{
+    constexpr int T = A * M / 16;
+    __shared__ __attribute__((aligned(16))) c2f cell[A * M];
+    const int tid = threadIdx.x;
+    const int slab = blockIdx.x, slabs = gridDim.x;
+    const int64_t row = blockIdx.y;
+    const int L = a.bins / M, a0 = slab * A;           // a0 + A <= L
+    const char *src = reinterpret_cast<const char *>(a.iq) + (a.first_row + row) * (int64_t)a.hop * BandSample<FMT>::BYTES;
+
+    // ---- samples: cell w = b A + t takes sample a0 + t + L b (< bins), all sixteen loads of a thread in flight
+    {
+        c2f x[16];
+        float wn[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int w = tid + T * i;                 // < A M
+            const int n = a0 + w % A + L * (w / A);
+            x[i] = BandSample<FMT>::load(src, n);
+            wn[i] = a.window[n];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            x[i].y += a.gain;                          // src/FFTBackend.cpp:78-79: Q += gain, then the window
+            cell[tid + T * i] = x[i] * wn[i];
+        }
+    }
+    __syncthreads();
+
+    // ---- the A transforms of M points
+    band_levels<M, A, M>(cell, a.tw, tid);
+
+    // ---- the slab's partial sum of every wanted column: A lanes per column, one per residue
+    const int t = tid % A, g = tid / A;
+    float2 *out = a.part + (row * slabs + slab) * (int64_t)a.cols;
+    for (int j0 = 0; j0 < a.cols; j0 += T / A) {
+        const int j = j0 + g;
+        const bool live = j < a.cols;
+        const int jj = live ? j : a.cols - 1;
+        const int k = (a.first_col + jj + a.bins / 2) & (a.bins - 1);
+        const c2f z = cell[band_pos<M>(k & (M - 1)) * A + t];
+        const float2 w1 = a.t1[jj * A + t];
+        c2f p = band_cmul(z, (c2f){w1.x, w1.y});
+#pragma unroll
+        for (int m = A / 2; m >= 1; m >>= 1) {         // the same tree on every launch
+            p.x += __shfl_xor(p.x, m, 64);
+            p.y += __shfl_xor(p.y, m, 64);
+        }
+        if (live && t == 0) {
+            const float2 w2 = a.t2[slab * a.cols + j];
+            p = band_cmul(p, (c2f){w2.x, w2.y});
+            out[j] = make_float2(p.x, p.y);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void band_finish_kernel(const float2 *__restrict__ part, float *__restrict__ band_out,
+                                                          int64_t band_stride, int cols, int slabs)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= cols) return;
+    const int64_t row = blockIdx.y;
+    const float2 *p = part + row * slabs * (int64_t)cols + j;
+    float re = 0.0f, im = 0.0f;
+    for (int s = 0; s < slabs; ++s) {                  // slab order, always
+        const float2 v = p[(int64_t)s * cols];
+        re += v.x;
+        im += v.y;
+    }
+    band_out[row * band_stride + j] = __builtin_amdgcn_sqrtf(re * re + im * im);
+}
+
+template <int M, int A> hipError_t launch_slab(int fmt, const BandArgs &a, int slabs, hipStream_t s)
+{
+    const dim3 grid((unsigned)slabs, (unsigned)a.rows), block(A * M / 16);
+    if (fmt == RO_FMT_I16) hipLaunchKernelGGL((band_slab_kernel<M, A, RO_FMT_I16>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((band_slab_kernel<M, A, RO_FMT_F32>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+bool band_plan(int bins, int cols, BandPlan &p)
+{
+    if (bins < 16384 || bins > 1048576 || (bins & (bins - 1)) != 0) return false;
+    if (cols < 1 || cols > 1024) return false;
+    p.m = cols <= 256 ? 256 : cols <= 512 ? 512 : 1024;
+    p.a = p.m == 1024 ? 8 : 16;
+    p.slabs = bins / (p.m * p.a);
+    return true;
+}
+
+hipError_t launch_band(const BandPlan &p, int fmt, const BandArgs &a, hipStream_t s)
+{
+    if (a.rows <= 0) return hipSuccess;
+    if (a.rows > 65535 || (fmt != RO_FMT_F32 && fmt != RO_FMT_I16)) return hipErrorInvalidValue;
+    hipError_t e = p.m == 256   ? launch_slab<256, 16>(fmt, a, p.slabs, s)
+                   : p.m == 512 ? launch_slab<512, 16>(fmt, a, p.slabs, s)
+                                : launch_slab<1024, 8>(fmt, a, p.slabs, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(band_finish_kernel, dim3((unsigned)((a.cols + 255) / 256), (unsigned)a.rows), dim3(256), 0, s,
+                       a.part, a.band_out, a.band_stride, a.cols, p.slabs);
+    return hipGetLastError();
+}
+
+}  // namespace ro

@@ -27,6 +27,7 @@
 
 #include "../../include/ro_stft.h"
 #include "ro_kernels.h"
+#include "ro_band.h"
 #include "ro_narrow.h"
 
 // a -DRO_DIAG=1 build (tools/ab_build.sh) reads its run-time knobs (RO_BIG_FORM, RO_F64_SCRATCH_MB) from the environment
@@ -222,6 +223,15 @@ struct ro_stft {
     // tile_ln: partial min / max of the fused epilogue's two tile waves (rows x 4 floats), grown on demand
     float  *d_ln_part = nullptr;
     int64_t ln_part_rows = 0;
+
+    // band-only transform (ro_stft_band_resident, ro_band.hip): the tables of the last band asked for, and the slabs'
+    // partial sums between its two kernels ([band_part_rows][slabs][cols] float2, grown on demand)
+    int     band_first = -1, band_cols = 0;
+    float2 *d_band_tw = nullptr;       // [m]: exp(-2 pi i j / m)
+    float2 *d_band_t1 = nullptr;       // [cols][a]: exp(-2 pi i t k / bins)
+    float2 *d_band_t2 = nullptr;       // [slabs][cols]: exp(-2 pi i (slab a) k / bins)
+    float2 *d_band_part = nullptr;
+    size_t  band_part_bytes = 0;
 
     // strict precision (RO_PRECISION_F64): double twiddle table + two complex-double scratch blocks
     bool     f64 = false;

@@ -763,6 +763,10 @@ extern "C" int ro_stft_destroy(ro_stft_t *h)
     for (int i = 0; i < 4; ++i)
         if (h->d_f64r_tw[i]) (void)hipFree(h->d_f64r_tw[i]);
     if (h->d_ln_part) (void)hipFree(h->d_ln_part);
+    if (h->d_band_tw) (void)hipFree(h->d_band_tw);
+    if (h->d_band_t1) (void)hipFree(h->d_band_t1);
+    if (h->d_band_t2) (void)hipFree(h->d_band_t2);
+    if (h->d_band_part) (void)hipFree(h->d_band_part);
     for (int i = 0; i < 2; ++i)
         if (h->d_scratch_d[i]) (void)hipFree(h->d_scratch_d[i]);
     if (h->d_f64_ring) (void)hipFree(h->d_f64_ring);
@@ -942,6 +946,165 @@ extern "C" int ro_stft_ln_tile_resident(ro_stft_t *h, const float *d_rows, int64
     a.first = first_col;
     a.cols = cols;
     HIP_TRY(ro::launch_ln_tile(a, (hipStream_t)stream));
+    return RO_OK;
+}
+
+// ---------------------------------------------------------------------------
+// band-only transform
+// ---------------------------------------------------------------------------
+extern "C" int ro_stft_band_supported(int bins, int cols)
+{
+    ro::BandPlan p;
+    return ro::band_plan(bins, cols, p) ? 1 : 0;
+}
+
+extern "C" int ro_bands_hull(const ro_bands_t *b, int bins, int tile_first_col, int tile_cols, int *first_col, int *cols)
+{
+    if (!b || !first_col || !cols) return fail(RO_ERR_INVALID, "ro_bands_hull: null argument");
+    if (b->noise_width <= 0 || b->detect_width <= 0 || b->avg_bins <= 0)
+        return fail(RO_ERR_INVALID, "bands: widths and avg_bins must be positive");
+    if (tile_cols < 0) return fail(RO_ERR_INVALID, "tile_cols must not be negative");
+    // average() reads avg_bins columns from low_detect + peak - avg_bins / 2, peak in [0, detect_width)
+    // (src/BolidRecorder.cpp:126-132)
+    int64_t lo = std::min<int64_t>(b->low_noise, (int64_t)b->low_detect - b->avg_bins / 2);
+    int64_t hi = std::max<int64_t>((int64_t)b->low_noise + b->noise_width,
+                                   (int64_t)b->low_detect + b->detect_width - 1 - b->avg_bins / 2 + b->avg_bins);
+    if (tile_cols > 0) {
+        lo = std::min<int64_t>(lo, tile_first_col);
+        hi = std::max<int64_t>(hi, (int64_t)tile_first_col + tile_cols);
+    }
+    if (lo < 0 || hi > bins)
+        return fail(RO_ERR_INVALID, "what the recorders read, columns [%lld,%lld), leaves the row [0,%d)", (long long)lo,
+                    (long long)hi, bins);
+    *first_col = (int)lo;
+    *cols = (int)(hi - lo);
+    return RO_OK;
+}
+
+namespace {
+
+// exp(-2 pi i e / n) for an exactly reduced integer phase e in [0, n), evaluated in double and narrowed once
+float2 unit_root(int64_t e, int64_t n)
+{
+    const double ang = -2.0 * M_PI * (double)e / (double)n;
+    return make_float2((float)cos(ang), (float)sin(ang));
+}
+
+// the tables of band [first_col, +cols), uploaded on first use and kept until another band is asked for
+int ensure_band_tables(ro_stft *h, const ro::BandPlan &p, int first_col, int cols)
+{
+    if (h->band_first == first_col && h->band_cols == cols) return RO_OK;
+    if (h->d_band_t1) {                                 // an earlier launch may still be reading the old tables
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(h->d_band_tw); h->d_band_tw = nullptr;
+        (void)hipFree(h->d_band_t1); h->d_band_t1 = nullptr;
+        (void)hipFree(h->d_band_t2); h->d_band_t2 = nullptr;
+        h->band_first = -1;
+        h->band_cols = 0;
+    }
+    const int64_t n = h->bins;
+    std::vector<float2> tw((size_t)p.m), t1((size_t)cols * p.a), t2((size_t)p.slabs * cols);
+    for (int j = 0; j < p.m; ++j) tw[(size_t)j] = unit_root(j, p.m);
+    for (int j = 0; j < cols; ++j) {
+        const int64_t k = ((int64_t)first_col + j + n / 2) % n;
+        for (int t = 0; t < p.a; ++t) t1[(size_t)j * p.a + t] = unit_root((t * k) % n, n);
+        for (int s = 0; s < p.slabs; ++s) t2[(size_t)s * cols + j] = unit_root(((int64_t)s * p.a * k) % n, n);
+    }
+    HIP_TRY(hipMalloc(&h->d_band_tw, sizeof(float2) * tw.size()));
+    HIP_TRY(hipMalloc(&h->d_band_t1, sizeof(float2) * t1.size()));
+    HIP_TRY(hipMalloc(&h->d_band_t2, sizeof(float2) * t2.size()));
+    HIP_TRY(hipMemcpy(h->d_band_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_band_t1, t1.data(), sizeof(float2) * t1.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_band_t2, t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice));
+    h->band_first = first_col;
+    h->band_cols = cols;
+    return RO_OK;
+}
+
+}  // namespace
+
+extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
+                                     int64_t rows, int first_col, int cols, float *d_band, int64_t band_stride,
+                                     ro_scan_record_t *d_records, void *stream)
+{
+    if (!h) return fail(RO_ERR_INVALID, "null handle");
+    if (h->f64) return fail(RO_ERR_UNSUPPORTED, "the band-only transform is float32: not for RO_PRECISION_F64 handles");
+    if (h->czt) return fail(RO_ERR_UNSUPPORTED, "the band-only transform needs power-of-two bins (got %d)", h->bins);
+    if (format == RO_IQ_F64) return fail(RO_ERR_UNSUPPORTED, "the band-only transform takes RO_IQ_F32 or RO_IQ_I16 samples");
+    if (format != RO_IQ_F32 && format != RO_IQ_I16)
+        return fail(RO_ERR_INVALID, "resident input must be RO_IQ_F32 or RO_IQ_I16 (got %d)", format);
+    ro::BandPlan p;
+    if (!ro::band_plan(h->bins, cols, p))
+        return fail(RO_ERR_UNSUPPORTED, "no band kernel for %d columns of %d bins (bins a power of two 16384 ... 1048576, "
+                                        "1 ... 1024 columns)", cols, h->bins);
+    if (first_col < 0 || (int64_t)first_col + cols > h->bins)
+        return fail(RO_ERR_INVALID, "band [%d,+%d) outside [0,%d)", first_col, cols, h->bins);
+    if (band_stride < cols) return fail(RO_ERR_INVALID, "band_stride %lld < cols %d", (long long)band_stride, cols);
+    if (rows < 0 || first_row < 0) return fail(RO_ERR_INVALID, "negative row range");
+    ro::ScanArgs sc{};
+    if (d_records) {
+        if (!h->cfg.enable_scan) return fail(RO_ERR_INVALID, "records requested but enable_scan == 0");
+        int lo = 0, n = 0;
+        const int rc = ro_bands_hull(&h->cfg.bands, h->bins, 0, 0, &lo, &n);
+        if (rc != RO_OK) return rc;
+        if (lo < first_col || lo + n > first_col + cols)
+            return fail(RO_ERR_INVALID, "records need columns [%d,%d) (the bands and the average's margin); the band is [%d,%d)",
+                        lo, lo + n, first_col, first_col + cols);
+        // the scan kernel of the full rows on the band image: the band is its row, the bands move by first_col
+        // (peak counts from low_detect and stays what it is)
+        sc = make_scan_args(h, d_band, band_stride, rows, d_records);
+        sc.bins = cols;
+        sc.low_noise -= first_col;
+        sc.low_detect -= first_col;
+    }
+    if (rows == 0) return RO_OK;
+    if (!d_iq) return fail(RO_ERR_INVALID, "null input pointer");
+    if (!d_band) return fail(RO_ERR_INVALID, "d_band is required");
+    const int64_t last = (first_row + rows - 1) * (int64_t)h->hop + h->bins;
+    if (last > samples)
+        return fail(RO_ERR_INVALID, "rows [%lld,+%lld) need %lld samples, buffer holds %lld", (long long)first_row,
+                    (long long)rows, (long long)last, (long long)samples);
+    if (rows > (int64_t)0x0fffffff) return fail(RO_ERR_INVALID, "too many rows in one launch");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = ensure_band_tables(h, p, first_col, cols);
+    if (rc != RO_OK) return rc;
+    // the partial sums: rows per chunk like the large transforms' scratch, 256 MiB at the most, one grid of <= 65535 rows
+    const size_t row_bytes = (size_t)p.slabs * cols * sizeof(float2);
+    const int64_t chunk = std::min<int64_t>(std::min<int64_t>(rows, 65535),
+                                            std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / row_bytes)));
+    if ((size_t)chunk * row_bytes > h->band_part_bytes) {
+        if (h->d_band_part) {                           // (an earlier launch may still be using the old block)
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipFree(h->d_band_part));
+            h->d_band_part = nullptr;
+            h->band_part_bytes = 0;
+        }
+        HIP_TRY(hipMalloc(&h->d_band_part, (size_t)chunk * row_bytes));
+        h->band_part_bytes = (size_t)chunk * row_bytes;
+    }
+    for (int64_t done = 0; done < rows; done += chunk) {
+        ro::BandArgs b{};
+        b.iq = d_iq;
+        b.window = h->d_window;
+        b.tw = h->d_band_tw;
+        b.t1 = h->d_band_t1;
+        b.t2 = h->d_band_t2;
+        b.part = h->d_band_part;
+        b.band_out = d_band + done * band_stride;
+        b.first_row = first_row + done;
+        b.rows = std::min(chunk, rows - done);
+        b.band_stride = band_stride;
+        b.hop = h->hop;
+        b.bins = h->bins;
+        b.first_col = first_col;
+        b.cols = cols;
+        b.gain = (float)h->cfg.iq_gain;
+        HIP_TRY(ro::launch_band(p, format, b, s));
+    }
+    if (d_records) HIP_TRY(ro::launch_scan(sc, s));
+    h->stat_launches += 1;
+    h->stat_rows += rows;
     return RO_OK;
 }
 

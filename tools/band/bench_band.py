@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""A/B of the band-only transform against the full-row path serving the same consumer, on resident inputs.
+
+  (a) run_resident: full rows + the snapshot tile + scan records  (what a host that feeds the recorders did before)
+  (b) band_resident: the hull of tile and bands + scan records
+
+One process; every shape is warmed up first; then the two legs alternate five times, each leg a HIP-event window of at
+least 0.5 s of back-to-back launches.  Shapes: Bolidozor.json (65536 / 49152, 4096 rows, the hull of its bands and its
+snapshot columns) and Ionozor.json's doppler configuration (524288 / 262144, 512 rows, 218 columns, no scan).
+
+Prints, per shape: rows/s of each leg with the spread of the five repeats, the ratio b / a, the share of the HBM peak
+the band's algorithmic bytes (hop x 8 + cols x 4 per row) make in (b), and the worst parity figure of both legs on the
+first 8 rows (max |x - oracle| / max of the full oracle row).
+
+    python tools/band/bench_band.py [--window 0.5] [--repeats 5]
+"""
+import argparse
+import importlib
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+
+HBM_PEAK_GBS = 8000.0            # the figure bench.py uses (HBM3E spec)
+
+
+def make_stream(torch, samples, bins, fs, first_col, cols, seed):
+    """sigma = 1 noise + amplitude 300 some 5000 columns outside the band + amplitude 3 inside it, made on the device"""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    iq = torch.randn((samples, 2), generator=g, device="cuda", dtype=torch.float32)
+    outside = first_col + cols + 5000 if first_col + cols + 5000 < bins else first_col - 5000
+    for col, amp in ((outside + 0.21, 300.0), (first_col + cols // 2 + 0.37, 3.0)):
+        w = 2.0 * math.pi * (col - bins / 2) / bins                       # radians per sample
+        for lo in range(0, samples, 1 << 24):
+            hi = min(samples, lo + (1 << 24))
+            ph = torch.arange(lo, hi, device="cuda", dtype=torch.float64) * w
+            iq[lo:hi, 0] += (amp * torch.cos(ph)).to(torch.float32)
+            iq[lo:hi, 1] += (amp * torch.sin(ph)).to(torch.float32)
+    return iq
+
+
+def timed(torch, launch, window_s):
+    """rows-independent: seconds per launch over a window of at least window_s"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    launch()
+    e1.record()
+    torch.cuda.synchronize()
+    iters = max(2, int(math.ceil(window_s / max(e0.elapsed_time(e1) * 1e-3, 1e-6))) + 1)
+    e0.record()
+    for _ in range(iters):
+        launch()
+    e1.record()
+    torch.cuda.synchronize()
+    total = e0.elapsed_time(e1) * 1e-3
+    return total / iters, total
+
+
+def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, args):
+    hop = bins - overlap
+    first_col, cols = band
+    samples = (rows - 1) * hop + bins
+    iq = make_stream(torch, samples, bins, fs, first_col, cols, seed=bins)
+    d_rows = torch.empty((rows, bins), dtype=torch.float32, device="cuda")
+    d_tile = torch.empty((rows, tile[1]), dtype=torch.float32, device="cuda")
+    d_band = torch.empty((rows, cols), dtype=torch.float32, device="cuda")
+    rec_a = torch.zeros((rows, 3), dtype=torch.float32, device="cuda") if bands is not None else None
+    rec_b = torch.zeros((rows, 3), dtype=torch.float32, device="cuda") if bands is not None else None
+    stream = torch.cuda.current_stream().cuda_stream
+    with ro.Stft(bins=bins, overlap=overlap, sample_rate=fs, bands=bands, tile=tile) as st:
+        def leg_a():
+            st.run_resident(iq, ro.RO_IQ_F32, samples, 0, rows, d_rows, d_tile=d_tile, d_records=rec_a, stream=stream)
+
+        def leg_b():
+            st.band_resident(iq, ro.RO_IQ_F32, samples, 0, rows, first_col, cols, d_band, d_records=rec_b, stream=stream)
+
+        for _ in range(2):                                              # warm-up: tables, scratch, clocks
+            leg_a()
+            leg_b()
+        torch.cuda.synchronize()
+        ta, tb, shortest = [], [], 1e9
+        for _ in range(args.repeats):
+            for leg, acc in ((leg_a, ta), (leg_b, tb)):
+                per, total = timed(torch, leg, args.window)
+                acc.append(rows / per)
+                shortest = min(shortest, total)
+    ta, tb = np.array(ta), np.array(tb)
+    # parity of both legs on the first 8 rows of the timed input
+    n8 = min(8, rows)
+    want = oracle.stft(iq[:(n8 - 1) * hop + bins].cpu().numpy(), bins, overlap, max_rows=n8).astype(np.float64)
+    ref = want.max(axis=1)
+    err_a = (np.abs(d_tile[:n8].cpu().numpy() - want[:, tile[0]:tile[0] + tile[1]]).max(axis=1) / ref).max()
+    err_b = (np.abs(d_band[:n8].cpu().numpy() - want[:, first_col:first_col + cols]).max(axis=1) / ref).max()
+    same_peaks = ""
+    if bands is not None:
+        pa = rec_a.cpu().numpy().view(ro.capi.SCAN_DTYPE)["peak"].reshape(-1)
+        pb = rec_b.cpu().numpy().view(ro.capi.SCAN_DTYPE)["peak"].reshape(-1)
+        same_peaks = "   peaks equal on %d of %d rows" % (int((pa == pb).sum()), rows)
+    alg = hop * 8 + cols * 4
+    spread = lambda x: (x.max() - x.min()) / np.median(x)
+    ratio = np.median(tb) / np.median(ta)
+    print("%s: %d bins / overlap %d, %d rows, band [%d,+%d), tile [%d,+%d), shortest window %.2f s" %
+          (name, bins, overlap, rows, first_col, cols, tile[0], tile[1], shortest))
+    print("  (a) full rows + tile%s: median %10.0f rows/s  (min %.0f, max %.0f, spread %.1f %%)" %
+          (" + records" if bands is not None else "", np.median(ta), ta.min(), ta.max(), 100 * spread(ta)))
+    print("  (b) band only%s:        median %10.0f rows/s  (min %.0f, max %.0f, spread %.1f %%)" %
+          (" + records" if bands is not None else "", np.median(tb), tb.min(), tb.max(), 100 * spread(tb)))
+    print("  b / a = %.2f   (slowest b / fastest a = %.2f)" % (ratio, tb.min() / ta.max()))
+    print("  (b) algorithmic bytes %d per row: %.1f GB/s = %.3f of the %.0f GB/s HBM peak" %
+          (alg, alg * np.median(tb) / 1e9, alg * np.median(tb) / 1e9 / HBM_PEAK_GBS, HBM_PEAK_GBS))
+    print("  parity on the first %d rows, max err / full row max: (a) %.2e  (b) %.2e%s" % (n8, err_a, err_b, same_peaks))
+    return tb.min() > ta.max()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--window", type=float, default=0.5, help="seconds of launches per timed leg, at least")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--rows-scale", type=float, default=1.0, help="scale both row counts (quick runs)")
+    args = ap.parse_args()
+    import torch
+    ro = importlib.import_module("radio-observer_amd")
+    import ro_oracle as oracle
+    oracle.lib()
+    ok = True
+    # Bolidozor.json:45-46, :75-76 (snapshot columns), :84-93 (bands; avg_freq_range at its default of 40 Hz)
+    bins, overlap, fs = 65536, 49152, 96000
+    b = oracle.bolid_bands(bins, fs, overlap, 26450, 26550, 26000, 26300, 5, 2, 40)
+    bands = ro.Bands(low_noise=b.low_noise, noise_width=b.noise_width, low_detect=b.low_detect,
+                     detect_width=b.detect_width, avg_bins=b.avg_bins)
+    t0, t1 = ro.frequency_to_bin(bins, fs, 26200.0), ro.frequency_to_bin(bins, fs, 26800.0)
+    tile = (t0, t1 - t0)
+    band = ro.bands_hull(bands, bins, *tile)
+    ok &= shape(torch, ro, oracle, "Bolidozor", bins, overlap, fs, max(8, int(4096 * args.rows_scale)), bands, tile, band, args)
+    # Ionozor.json:27-28, the doppler recorder's 40 Hz around 10.6 kHz: no scan
+    bins, overlap = 524288, 262144
+    band = (ro.frequency_to_bin(bins, fs, 10580.0), 218)
+    ok &= shape(torch, ro, oracle, "Ionozor doppler", bins, overlap, fs, max(8, int(512 * args.rows_scale)), None, band, band, args)
+    print("band only faster than full rows at both shapes by more than the repeats' spread: %s" % ("yes" if ok else "NO"))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
