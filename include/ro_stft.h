@@ -209,6 +209,20 @@ int ro_stft_bins(const ro_stft_t *h);
 int ro_stft_device_name(const ro_stft_t *h, char *buf, size_t len);
 int ro_stft_set_bands(ro_stft_t *h, const ro_bands_t *bands);
 
+/* ---- several band sets per row: one record per detector -----------------------
+ * WaterfallBackend keeps a vector of recorders and calls every one of them for every row (src/WaterfallBackend.cpp:534-536,
+ * :563-567), and each BolidRecorder derives its own noise band, detect band and averaging range in start()
+ * (src/BolidRecorder.cpp:84-104): several detectors on one stream, each watching another frequency window.  A handle
+ * serves up to 8 of them in one pass: the band set of ro_stft_config_t::bands / ro_stft_set_bands (the PRIMARY, unchanged
+ * in every respect) and up to RO_MAX_EXTRA_BANDS extra sets, scanned from the rows the transform has just written. */
+#define RO_MAX_EXTRA_BANDS 7
+/* 0 <= count <= 7; count = 0 removes them.  Needs a primary set (enable_scan), else RO_ERR_STATE.
+ * Every set is checked like ro_stft_set_bands; the message names the offending set's index.
+ * count outside 0..7 gives RO_ERR_INVALID.  Only on an idle stream (nothing staged, nothing waiting
+ * to be fetched), else RO_ERR_STATE.  Changing the sets drops the slots' captured graphs. */
+int ro_stft_set_extra_bands(ro_stft_t *h, const ro_bands_t *sets, int count);
+int ro_stft_extra_bands(const ro_stft_t *h, ro_bands_t *sets_out /* may be NULL */);   /* returns count */
+
 /* ---- resident path (benchmarks, multi-GPU shards) --------------------------
  * Replaces, for rows [first_row, first_row+rows) of a stream that is already in
  * HBM, the whole of FFTBackend::process's row loop (src/FFTBackend.cpp:211-257)
@@ -229,6 +243,12 @@ int ro_stft_run_resident(ro_stft_t *h, const void *d_iq, int format, int64_t sam
                          int64_t first_row, int64_t rows,
                          float *d_rows, int64_t row_stride,
                          float *d_tile, ro_scan_record_t *d_records, void *stream);
+
+/* ro_stft_run_resident plus d_extra: device, rows x count records, record of extra set s of row r at [r * count + s].
+ * d_extra == NULL behaves exactly like ro_stft_run_resident.  d_extra != NULL with count == 0 gives RO_ERR_STATE. */
+int ro_stft_run_resident_sets(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row, int64_t rows,
+                              float *d_rows, int64_t row_stride, float *d_tile,
+                              ro_scan_record_t *d_records, ro_scan_record_t *d_extra, void *stream);
 
 /* ro_stft_run_resident plus the viewer's log image of the tile, produced by the transform itself (tile_ln = 1):
  *   d_ln_tile    device, rows x tile_cols floats: logf(pixel) of every tile pixel (-inf for a zero pixel)
@@ -264,6 +284,10 @@ int ro_stft_spectra_resident(ro_stft_t *h, const void *d_iq, int format, int64_t
 int ro_stft_scan_resident(ro_stft_t *h, const float *d_rows, int64_t row_stride, int64_t rows,
                           ro_scan_record_t *d_records, void *stream);
 
+/* ro_stft_scan_resident for all sets: d_records (primary) may be NULL, d_extra is required */
+int ro_stft_scan_sets_resident(ro_stft_t *h, const float *d_rows, int64_t row_stride, int64_t rows,
+                               ro_scan_record_t *d_records, ro_scan_record_t *d_extra, void *stream);
+
 /* The offline viewer's transform of a band image, on rows already in HBM (fits2png:46 FN_LOG,
  * :444-445 default_color_fn, :476-477 min/max, :495-497 the uint8 store):
  *   ln    = logf(pixel), float32, over columns [first_col, first_col+cols) of `rows` rows
@@ -290,7 +314,8 @@ int ro_stft_band_supported(int bins, int cols);
  * src/BolidRecorder.cpp:313-317), the detect band (peak(), :323-335) widened by what average() reads around any peak
  * (:126-132, :338-347: [low_detect - avg_bins/2, low_detect + detect_width - 1 - avg_bins/2 + avg_bins)), and, if
  * tile_cols > 0, the tile (the snapshot's column cut, src/WaterfallBackend.cpp:176,204).
- * RO_ERR_INVALID if that range leaves [0, bins).  Pure host. */
+ * RO_ERR_INVALID if that range leaves [0, bins).  Pure host.  ONE band set: the band-only transform's records stay
+ * single-set (the primary), and a hull over a handle's extra sets (ro_stft_set_extra_bands) is out of scope. */
 int ro_bands_hull(const ro_bands_t *bands, int bins, int tile_first_col, int tile_cols,
                   int *first_col, int *cols);
 
@@ -339,6 +364,11 @@ int ro_stft_flush(ro_stft_t *h, int64_t *rows_ready);
 int ro_stft_fetch(ro_stft_t *h, int64_t max_rows, int first_col, int cols,
                   float *rows_out, ro_scan_record_t *records_out,
                   int64_t *first_row_index, int64_t *rows_got);
+/* ro_stft_fetch plus extra_out: host, max_rows x count records in the same row-major layout, or NULL.  (ro_stft_fetch and
+ * ro_stft_fetch_ln hand out the primary record only; a batch's extra records go with its rows.) */
+int ro_stft_fetch_sets(ro_stft_t *h, int64_t max_rows, int first_col, int cols, float *rows_out,
+                       ro_scan_record_t *records_out, ro_scan_record_t *extra_out,
+                       int64_t *first_row_index, int64_t *rows_got);
 /* Rows at the head of the output queue whose batches have finished on the device, download included: ro_stft_fetch
  * hands these over without waiting (it WAITS for anything beyond them).  A host that fetches only what is complete
  * keeps the next batch in flight under the previous one's download and under its own per-row work -- the recorders

@@ -14,6 +14,7 @@ from . import build as _build
 RO_WINDOW_NUTTALL, RO_WINDOW_HANN, RO_WINDOW_CUSTOM = 0, 1, 2
 RO_IQ_F32, RO_IQ_I16, RO_IQ_F64 = 0, 1, 2
 RO_PRECISION_F32, RO_PRECISION_F64 = 0, 1
+RO_MAX_EXTRA_BANDS = 7
 
 RO_OK = 0
 _ERR_NAMES = {-1: "RO_ERR_INVALID", -2: "RO_ERR_UNSUPPORTED", -3: "RO_ERR_HIP", -4: "RO_ERR_NOMEM",
@@ -92,6 +93,15 @@ _EXPORTS = {
     "ro_stft_bins": (C.c_int, [C.c_void_p]),
     "ro_stft_device_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "ro_stft_set_bands": (C.c_int, [C.c_void_p, C.POINTER(Bands)]),
+    "ro_stft_set_extra_bands": (C.c_int, [C.c_void_p, C.POINTER(Bands), C.c_int]),
+    "ro_stft_extra_bands": (C.c_int, [C.c_void_p, C.POINTER(Bands)]),
+    "ro_stft_run_resident_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ro_stft_scan_sets_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "ro_stft_fetch_sets": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                     C.POINTER(ScanRecord), C.POINTER(ScanRecord), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64)]),
     "ro_stft_run_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ro_stft_run_resident_ln": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
@@ -328,7 +338,8 @@ class Stft:
 
     def __init__(self, bins=32768, overlap=0, sample_rate=48000, window=RO_WINDOW_NUTTALL,
                  window_table=None, iq_gain=0.0, iq_phase_shift=0, device=0, max_batch_rows=0,
-                 bands=None, tile=None, spare_cus_per_xcd=0, precision=RO_PRECISION_F32, tile_ln=False):
+                 bands=None, tile=None, spare_cus_per_xcd=0, precision=RO_PRECISION_F32, tile_ln=False,
+                 extra_bands=None):
         cfg = Config()
         cfg.struct_size = C.sizeof(Config)
         cfg.bins, cfg.overlap, cfg.sample_rate = bins, overlap, sample_rate
@@ -360,6 +371,13 @@ class Stft:
         self.hop = library().ro_stft_hop(self._h)
         self.scan_enabled = bands is not None
         self.tile = tile
+        self.extra_count = 0
+        if extra_bands:
+            try:
+                self.set_extra_bands(extra_bands)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -394,7 +412,35 @@ class Stft:
         _check(library().ro_stft_set_bands(self._h, C.byref(bands)))
         self.scan_enabled = True
 
+    def set_extra_bands(self, sets):
+        """up to RO_MAX_EXTRA_BANDS more band sets scanned for every row beside the primary (one per further detector);
+        an empty list removes them -- ro_stft_set_extra_bands"""
+        sets = list(sets or [])
+        arr = (Bands * max(len(sets), 1))(*sets)
+        _check(library().ro_stft_set_extra_bands(self._h, arr, len(sets)))
+        self.extra_count = len(sets)
+
+    @property
+    def extra_bands(self):
+        arr = (Bands * RO_MAX_EXTRA_BANDS)()
+        n = library().ro_stft_extra_bands(self._h, arr)
+        if n < 0:
+            _check(n)
+        return [arr[i] for i in range(n)]
+
     # -- resident path
+    def run_resident_sets(self, d_iq, fmt, samples, first_row, rows, d_rows, row_stride=None, d_tile=None,
+                          d_records=None, d_extra=None, stream=None):
+        """run_resident + d_extra: rows x extra_count records, set s of row r at [r * extra_count + s]"""
+        _check(library().ro_stft_run_resident_sets(self._h, _ptr(d_iq), fmt, samples, first_row, rows,
+                                                   _ptr(d_rows), row_stride or self.bins, _ptr(d_tile),
+                                                   _ptr(d_records), _ptr(d_extra), _ptr(stream)))
+
+    def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
+        """scan_resident for the extra sets (and the primary too when d_records is given)"""
+        _check(library().ro_stft_scan_sets_resident(self._h, _ptr(d_rows), row_stride or self.bins, rows,
+                                                    _ptr(d_records), _ptr(d_extra), _ptr(stream)))
+
     def run_resident(self, d_iq, fmt, samples, first_row, rows, d_rows, row_stride=None, d_tile=None,
                      d_records=None, stream=None):
         _check(library().ro_stft_run_resident(self._h, _ptr(d_iq), fmt, samples, first_row, rows,
@@ -494,6 +540,29 @@ class Stft:
             C.byref(first), C.byref(got)))
         g = got.value
         return first.value, rows[:g], (recs[:g] if recs is not None else None)
+
+    def fetch_sets(self, max_rows, first_col=None, cols=None, want_rows=None, want_extra=True):
+        """ro_stft_fetch_sets: (first_row_index, rows, records, extra) with extra shaped (rows_got, extra_count); rows is
+        None for a handle with a row sink (they are in the ring), records None without a primary set"""
+        if first_col is None:
+            first_col = self.tile[0] if self.tile else 0
+        if cols is None:
+            cols = (self.tile[0] + self.tile[1] - first_col) if self.tile else self.bins - first_col
+        want_rows = (getattr(self, "_sink", None) is None) if want_rows is None else want_rows
+        rows = np.empty((max_rows, cols), dtype=np.float32) if want_rows else None
+        recs = np.empty(max_rows, dtype=SCAN_DTYPE) if self.scan_enabled else None
+        count = self.extra_count
+        extra = np.empty((max_rows, max(count, 1)), dtype=SCAN_DTYPE) if want_extra else None
+        first, got = C.c_int64(), C.c_int64()
+        _check(library().ro_stft_fetch_sets(
+            self._h, max_rows, first_col if want_rows else 0, cols if want_rows else 0,
+            rows.ctypes.data_as(C.POINTER(C.c_float)) if rows is not None else None,
+            recs.ctypes.data_as(C.POINTER(ScanRecord)) if recs is not None else None,
+            extra.ctypes.data_as(C.POINTER(ScanRecord)) if extra is not None else None,
+            C.byref(first), C.byref(got)))
+        g = got.value
+        return (first.value, rows[:g] if rows is not None else None, recs[:g] if recs is not None else None,
+                extra[:g, :count] if extra is not None else None)
 
     def reset(self):
         _check(library().ro_stft_reset(self._h))

@@ -110,6 +110,7 @@ struct Batch {
     float *ln = nullptr;                       // capacity_rows x out_cols (tile_ln), pinned
     float *minmax = nullptr;                   // capacity_rows x 2 (tile_ln), pinned
     ro_scan_record_t *records = nullptr;       // capacity_rows, pinned
+    ro_scan_record_t *extra = nullptr;         // capacity_rows x extra_count (extra band sets), pinned
     int64_t capacity_rows = 0;
     int64_t consumed = 0;                      // rows already fetched
     hipEvent_t done = nullptr;
@@ -133,6 +134,9 @@ struct ro_stft {
     float2 *d_twiddles = nullptr;
     float4 *d_twiddles_k = nullptr;    // packed copy for the radix-16/32 stages
     hipStream_t stream = nullptr;
+    // extra band sets (ro_stft_set_extra_bands): scanned by ro_scan_sets.hip behind the primary's scan
+    ro_bands_t extra[RO_MAX_EXTRA_BANDS] = {};
+    int        extra_count = 0;
 
     // streaming state.  Three HIP streams and RO_STREAM_SLOTS slots of device buffers: while the kernels of batch n run on
     // `stream`, batch n+1 is uploaded on `s_in` and batch n-1 goes home on `s_out`.
@@ -154,6 +158,7 @@ struct ro_stft {
         float *d_ln = nullptr;                 // ... its log and the rows' min / max of it (tile_ln)
         float *d_minmax = nullptr;
         ro_scan_record_t *d_records = nullptr;
+        ro_scan_record_t *d_extra = nullptr;   // batch_rows x extra_count: the extra band sets' records
         void  *h_in = nullptr;                 // pinned upload staging
         hipEvent_t uploaded = nullptr;         // H2D of this slot done (h_in reusable, kernels may start)
         hipEvent_t staging_free = nullptr;     // what the host waits for before it writes h_in again: `uploaded`, or the `done`
@@ -268,8 +273,11 @@ int launch_transform(ro_stft *h, const void *d_iq, int format, int64_t first_row
                      int64_t row_stride, hipStream_t s, float *d_tile = nullptr, ro_scan_record_t *d_records = nullptr,
                      float *d_ln = nullptr);
 // d_ln / d_minmax: the tile's log and the rows' min / max of it (tile_ln); need d_tile
+// d_extra: rows x extra_count records of the handle's extra band sets (null: nothing is launched for them)
 int launch_tile_and_scan(ro_stft *h, const float *d_rows, int64_t row_stride, int64_t rows, float *d_tile,
-                         ro_scan_record_t *d_records, hipStream_t s, float *d_ln = nullptr, float *d_minmax = nullptr);
+                         ro_scan_record_t *d_records, hipStream_t s, float *d_ln = nullptr, float *d_minmax = nullptr,
+                         ro_scan_record_t *d_extra = nullptr);
+int check_bands(const ro_stft *h, const ro_bands_t &b);
 int ensure_ln_part(ro_stft *h, int64_t rows);
 int launch_spectra_big(ro_stft *h, const void *d_iq, int format, int64_t first_row, int64_t rows, float2 *d_out,
                        int64_t out_stride, hipStream_t s);

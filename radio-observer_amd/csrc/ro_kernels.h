@@ -80,6 +80,17 @@ struct ScanArgs {
     int               avg_bins;
 };
 
+// the extra band sets of a handle (ro_stft_set_extra_bands), scanned by ro_scan_sets.hip: one wavefront per (row, set)
+struct ScanSetsArgs {
+    const float      *rows_in;
+    ro_scan_record_t *extra;       // rows x count, the record of set s of row r at [r * count + s]
+    int64_t           rows;
+    int64_t           row_stride;
+    int               bins;
+    int               count;       // 1 ... RO_MAX_EXTRA_BANDS
+    ro_bands_t        sets[RO_MAX_EXTRA_BANDS];
+};
+
 // ---- strict precision (RO_PRECISION_F64): the Stockham recurrence as separate radix-16 passes in double, any power of two
 struct BigArgsD {
     const void    *iq;         // FIRST pass: sample 0 of the stream
@@ -215,6 +226,7 @@ void       stft32k_window_layout(const float *w, float *out);         // host: 3
 // (diagnostic builds only: tools/r3/ro_stft_wl.hip, the same structure at N = 16384 / 8192)
 hipError_t launch_stft_wl(int bins, int fmt, const StftArgs &a, hipStream_t s);
 hipError_t launch_scan(const ScanArgs &a, hipStream_t s);
+hipError_t launch_scan_sets(const ScanSetsArgs &a, hipStream_t s);      // ro_scan_sets.hip
 hipError_t launch_tile(const TileArgs &a, hipStream_t s);
 hipError_t launch_ln_tile(const LnArgs &a, hipStream_t s);
 // per-row log of a compact tile + min / max (plans without the fused epilogue), and the fold of the fused partials

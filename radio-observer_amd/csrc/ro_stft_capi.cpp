@@ -42,19 +42,6 @@ std::vector<double2> build_full_twiddles_f64(int bins)
     return tw;
 }
 
-int check_bands(const ro_stft *h, const ro_bands_t &b)
-{
-    if (b.noise_width <= 0 || b.detect_width <= 0 || b.avg_bins <= 0)
-        return fail(RO_ERR_INVALID, "bands: widths and avg_bins must be positive");
-    if (b.low_noise < 0 || b.low_noise + b.noise_width > h->bins)
-        return fail(RO_ERR_INVALID, "bands: noise band [%d,+%d) outside [0,%d)", b.low_noise,
-                    b.noise_width, h->bins);
-    if (b.low_detect < 0 || b.low_detect + b.detect_width > h->bins)
-        return fail(RO_ERR_INVALID, "bands: detect band [%d,+%d) outside [0,%d)", b.low_detect,
-                    b.detect_width, h->bins);
-    return RO_OK;
-}
-
 int validate_resident(const ro_stft *h, const void *d_iq, int format, int64_t samples,
                       int64_t first_row, int64_t rows, const float *d_rows, int64_t row_stride,
                       const float *d_tile, const ro_scan_record_t *d_records)
@@ -109,6 +96,20 @@ ro::ScanArgs make_scan_args(const ro_stft *h, const float *d_rows, int64_t row_s
     s.low_detect = h->cfg.bands.low_detect;
     s.detect_width = h->cfg.bands.detect_width;
     s.avg_bins = h->cfg.bands.avg_bins;
+    return s;
+}
+
+ro::ScanSetsArgs make_scan_sets_args(const ro_stft *h, const float *d_rows, int64_t row_stride, int64_t rows,
+                                     ro_scan_record_t *d_extra)
+{
+    ro::ScanSetsArgs s{};
+    s.rows_in = d_rows;
+    s.extra = d_extra;
+    s.rows = rows;
+    s.row_stride = row_stride;
+    s.bins = h->bins;
+    s.count = h->extra_count;
+    for (int i = 0; i < h->extra_count; ++i) s.sets[i] = h->extra[i];
     return s;
 }
 
@@ -244,6 +245,19 @@ int launch_transform_f64(ro_stft *h, const void *d_iq, int format, int64_t first
 namespace ro {
 namespace host {
 
+int check_bands(const ro_stft *h, const ro_bands_t &b)
+{
+    if (b.noise_width <= 0 || b.detect_width <= 0 || b.avg_bins <= 0)
+        return fail(RO_ERR_INVALID, "bands: widths and avg_bins must be positive");
+    if (b.low_noise < 0 || b.low_noise + b.noise_width > h->bins)
+        return fail(RO_ERR_INVALID, "bands: noise band [%d,+%d) outside [0,%d)", b.low_noise,
+                    b.noise_width, h->bins);
+    if (b.low_detect < 0 || b.low_detect + b.detect_width > h->bins)
+        return fail(RO_ERR_INVALID, "bands: detect band [%d,+%d) outside [0,%d)", b.low_detect,
+                    b.detect_width, h->bins);
+    return RO_OK;
+}
+
 ro::StftArgs make_stft_args(const ro_stft *h, const void *d_iq, int64_t first_row, int64_t rows,
                             float *d_rows, int64_t row_stride, float *d_tile,
                             ro_scan_record_t *d_records, float *d_ln)
@@ -282,16 +296,19 @@ ro::StftArgs make_stft_args(const ro_stft *h, const void *d_iq, int64_t first_ro
 
 // d_ln / d_minmax: the tile's log and the rows' min / max of it (tile_ln); need d_tile
 int launch_tile_and_scan(ro_stft *h, const float *d_rows, int64_t row_stride, int64_t rows, float *d_tile,
-                         ro_scan_record_t *d_records, hipStream_t s, float *d_ln, float *d_minmax)
+                         ro_scan_record_t *d_records, hipStream_t s, float *d_ln, float *d_minmax, ro_scan_record_t *d_extra)
 {
     const bool want_ln = d_tile && (d_ln || d_minmax);
     if (!h->f64 && ro::stft_fuses_scan(h->bins)) {                  // tile, log and records written by the transform
         if (want_ln && d_minmax) HIP_TRY(ro::launch_ln_finish(h->d_ln_part, d_minmax, rows, s));
-        return RO_OK;
+    } else {
+        if (d_tile) HIP_TRY(ro::launch_tile(make_tile_args(h, d_rows, row_stride, rows, d_tile), s));
+        if (want_ln) HIP_TRY(ro::launch_ln_rows(d_tile, d_ln, d_minmax, rows, h->cfg.tile_cols, s));
+        if (d_records) HIP_TRY(ro::launch_scan(make_scan_args(h, d_rows, row_stride, rows, d_records), s));
     }
-    if (d_tile) HIP_TRY(ro::launch_tile(make_tile_args(h, d_rows, row_stride, rows, d_tile), s));
-    if (want_ln) HIP_TRY(ro::launch_ln_rows(d_tile, d_ln, d_minmax, rows, h->cfg.tile_cols, s));
-    if (d_records) HIP_TRY(ro::launch_scan(make_scan_args(h, d_rows, row_stride, rows, d_records), s));
+    // the extra band sets, from the rows in HBM whatever wrote the primary's record (the fused epilogue is frozen)
+    if (d_extra && h->extra_count > 0)
+        HIP_TRY(ro::launch_scan_sets(make_scan_sets_args(h, d_rows, row_stride, rows, d_extra), s));
     return RO_OK;
 }
 
@@ -831,22 +848,40 @@ extern "C" int ro_stft_set_bands(ro_stft_t *h, const ro_bands_t *bands)
 // ---------------------------------------------------------------------------
 // resident path
 // ---------------------------------------------------------------------------
-extern "C" int ro_stft_run_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples,
-                                    int64_t first_row, int64_t rows, float *d_rows, int64_t row_stride,
-                                    float *d_tile, ro_scan_record_t *d_records, void *stream)
+// ro_stft_run_resident and ro_stft_run_resident_sets: the same launches, plus scan_sets_kernel when d_extra is given
+static int run_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row, int64_t rows,
+                        float *d_rows, int64_t row_stride, float *d_tile, ro_scan_record_t *d_records,
+                        ro_scan_record_t *d_extra, void *stream)
 {
     int rc = validate_resident(h, d_iq, format, samples, first_row, rows, d_rows, row_stride, d_tile,
                                d_records);
-    if (rc != RO_OK || rows == 0) return rc;
+    if (rc != RO_OK) return rc;
+    if (d_extra && h->extra_count == 0)
+        return fail(RO_ERR_STATE, "extra records requested but no extra band sets are set (ro_stft_set_extra_bands)");
+    if (rows == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;      // NULL = the default (null) stream, like any HIP launch
     rc = launch_transform(h, d_iq, format, first_row, rows, d_rows, row_stride, s, d_tile, d_records);
     if (rc != RO_OK) return rc;
-    rc = launch_tile_and_scan(h, d_rows, row_stride, rows, d_tile, d_records, s);
+    rc = launch_tile_and_scan(h, d_rows, row_stride, rows, d_tile, d_records, s, nullptr, nullptr, d_extra);
     if (rc != RO_OK) return rc;
     h->stat_launches += 1;
     h->stat_rows += rows;
     return RO_OK;
+}
+
+extern "C" int ro_stft_run_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples,
+                                    int64_t first_row, int64_t rows, float *d_rows, int64_t row_stride,
+                                    float *d_tile, ro_scan_record_t *d_records, void *stream)
+{
+    return run_resident(h, d_iq, format, samples, first_row, rows, d_rows, row_stride, d_tile, d_records, nullptr, stream);
+}
+
+extern "C" int ro_stft_run_resident_sets(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
+                                         int64_t rows, float *d_rows, int64_t row_stride, float *d_tile,
+                                         ro_scan_record_t *d_records, ro_scan_record_t *d_extra, void *stream)
+{
+    return run_resident(h, d_iq, format, samples, first_row, rows, d_rows, row_stride, d_tile, d_records, d_extra, stream);
 }
 
 extern "C" int ro_stft_run_resident_ln(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
@@ -923,6 +958,29 @@ extern "C" int ro_stft_scan_resident(ro_stft_t *h, const float *d_rows, int64_t 
     ro::ScanArgs sc = make_scan_args(h, d_rows, row_stride, rows, d_records);
     HIP_TRY(ro::launch_scan(sc, s));
     return RO_OK;
+}
+
+extern "C" int ro_stft_scan_sets_resident(ro_stft_t *h, const float *d_rows, int64_t row_stride, int64_t rows,
+                                          ro_scan_record_t *d_records, ro_scan_record_t *d_extra, void *stream)
+{
+    if (!h || !d_rows || !d_extra) return fail(RO_ERR_INVALID, "null argument");
+    if (!h->cfg.enable_scan) return fail(RO_ERR_STATE, "scan bands not configured");
+    if (h->extra_count == 0) return fail(RO_ERR_STATE, "no extra band sets are set (ro_stft_set_extra_bands)");
+    if (rows < 0 || row_stride < h->bins) return fail(RO_ERR_INVALID, "bad rows / row_stride");
+    if (rows > (int64_t)0x0fffffff) return fail(RO_ERR_INVALID, "too many rows in one launch");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (d_records) HIP_TRY(ro::launch_scan(make_scan_args(h, d_rows, row_stride, rows, d_records), s));
+    HIP_TRY(ro::launch_scan_sets(make_scan_sets_args(h, d_rows, row_stride, rows, d_extra), s));
+    return RO_OK;
+}
+
+extern "C" int ro_stft_extra_bands(const ro_stft_t *h, ro_bands_t *sets_out)
+{
+    if (!h) return fail(RO_ERR_INVALID, "null handle");
+    if (sets_out)
+        for (int i = 0; i < h->extra_count; ++i) sets_out[i] = h->extra[i];
+    return h->extra_count;
 }
 
 extern "C" int ro_stft_ln_tile_resident(ro_stft_t *h, const float *d_rows, int64_t row_stride, int64_t rows,

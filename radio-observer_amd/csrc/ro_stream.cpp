@@ -23,6 +23,9 @@ Batch *acquire_batch(ro_stft *h)
                        hipHostMallocDefault) != hipSuccess) ||
         hipHostMalloc(reinterpret_cast<void **>(&b->records), (size_t)b->capacity_rows * sizeof(ro_scan_record_t),
                       hipHostMallocDefault) != hipSuccess ||
+        (h->extra_count > 0 &&
+         hipHostMalloc(reinterpret_cast<void **>(&b->extra),
+                       (size_t)b->capacity_rows * h->extra_count * sizeof(ro_scan_record_t), hipHostMallocDefault) != hipSuccess) ||
         (h->cfg.tile_ln &&
          (hipHostMalloc(reinterpret_cast<void **>(&b->ln), (size_t)b->capacity_rows * h->out_cols * sizeof(float),
                         hipHostMallocDefault) != hipSuccess ||
@@ -34,6 +37,7 @@ Batch *acquire_batch(ro_stft *h)
         if (b->ln) (void)hipHostFree(b->ln);
         if (b->minmax) (void)hipHostFree(b->minmax);
         if (b->records) (void)hipHostFree(b->records);
+        if (b->extra) (void)hipHostFree(b->extra);
         if (b->done) (void)hipEventDestroy(b->done);
         if (b->k0) (void)hipEventDestroy(b->k0);
         if (b->k1) (void)hipEventDestroy(b->k1);
@@ -79,6 +83,8 @@ int ensure_stream_slots(ro_stft *h)
             ok(hipEventCreateWithFlags(&sl.drained, hipEventDisableTiming));
         if (h->cfg.tile_cols > 0)
             ok(hipMalloc(&sl.d_tile, (size_t)h->batch_rows * h->cfg.tile_cols * sizeof(float)));
+        if (h->extra_count > 0)
+            ok(hipMalloc(&sl.d_extra, (size_t)h->batch_rows * h->extra_count * sizeof(ro_scan_record_t)));
         if (h->cfg.tile_ln)
             ok(hipMalloc(&sl.d_ln, (size_t)h->batch_rows * h->cfg.tile_cols * sizeof(float))) &&
                 ok(hipMalloc(&sl.d_minmax, (size_t)h->batch_rows * 2 * sizeof(float)));
@@ -161,6 +167,10 @@ int run_stream_batch(ro_stft *h, int64_t rows)
     bool graphed = RO_STREAM_GRAPH && small && h->sink && !h->cfg.tile_ln && (!h->f64 || h->f64reg) && !h->czt && !h->four &&
                    rows == h->batch_rows && sl.uses > 0;
     ro_scan_record_t *g_recs = h->cfg.enable_scan ? sl.d_records : nullptr;
+    // (the extra band sets: one more kernel behind the primary's scan -- one more node in the graph's chain -- and one
+    // more copy home beside the primary records'; ro_stft_set_extra_bands drops the graphs, whose kernel arguments hold the bands)
+    ro_scan_record_t *g_ext = h->extra_count > 0 ? sl.d_extra : nullptr;
+    const size_t ext_bytes = (size_t)rows * (size_t)h->extra_count * sizeof(ro_scan_record_t);
     if (graphed && (!sl.gexec || sl.graph_fmt != h->stage_fmt)) {
         if (sl.gexec) { (void)hipGraphExecDestroy(sl.gexec); sl.gexec = nullptr; }
         if (!sl.gstream) step(hipStreamCreateWithFlags(&sl.gstream, hipStreamNonBlocking), "hipStreamCreateWithFlags");
@@ -171,7 +181,7 @@ int run_stream_batch(ro_stft *h, int64_t rows)
         if (rc == RO_OK && step(hipStreamBeginCapture(sl.gstream, hipStreamCaptureModeThreadLocal), "hipStreamBeginCapture")) {
             step(hipMemcpyAsync(sl.d_iq, sl.h_in, (size_t)need * sb, hipMemcpyHostToDevice, sl.gstream), "upload");
             if (rc == RO_OK) rc = launch_transform(h, sl.d_iq, h->stage_fmt, 0, rows, sl.d_rows, h->bins, sl.gstream, sl.d_tile, g_recs, sl.d_ln);
-            if (rc == RO_OK) rc = launch_tile_and_scan(h, sl.d_rows, h->bins, rows, sl.d_tile, g_recs, sl.gstream, sl.d_ln, sl.d_minmax);
+            if (rc == RO_OK) rc = launch_tile_and_scan(h, sl.d_rows, h->bins, rows, sl.d_tile, g_recs, sl.gstream, sl.d_ln, sl.d_minmax, g_ext);
             const hipError_t ce = hipStreamEndCapture(sl.gstream, &g);          // (always: leaves capture mode)
             if (rc == RO_OK) step(ce, "hipStreamEndCapture");
             if (rc == RO_OK) step(hipGraphInstantiate(&sl.gexec, g, nullptr, nullptr, 0), "hipGraphInstantiate");
@@ -213,7 +223,7 @@ int run_stream_batch(ro_stft *h, int64_t rows)
         if (h->diag_direct) {                       // the graph's calls made one by one on the slot's stream
             step(hipMemcpyAsync(sl.d_iq, sl.h_in, (size_t)need * sb, hipMemcpyHostToDevice, gs), "upload");
             if (rc == RO_OK) rc = launch_transform(h, sl.d_iq, h->stage_fmt, 0, rows, sl.d_rows, h->bins, gs, sl.d_tile, g_recs, sl.d_ln);
-            if (rc == RO_OK) rc = launch_tile_and_scan(h, sl.d_rows, h->bins, rows, sl.d_tile, g_recs, gs, sl.d_ln, sl.d_minmax);
+            if (rc == RO_OK) rc = launch_tile_and_scan(h, sl.d_rows, h->bins, rows, sl.d_tile, g_recs, gs, sl.d_ln, sl.d_minmax, g_ext);
         } else {
             step(hipGraphLaunch(sl.gexec, gs), "hipGraphLaunch");
         }
@@ -237,6 +247,7 @@ int run_stream_batch(ro_stft *h, int64_t rows)
             if (h->cfg.enable_scan)
                 step(hipMemcpyAsync(b->records, sl.d_records, (size_t)rows * sizeof(ro_scan_record_t), hipMemcpyDeviceToHost, gs),
                      "download");
+            if (g_ext) step(hipMemcpyAsync(b->extra, sl.d_extra, ext_bytes, hipMemcpyDeviceToHost, gs), "download");
         }
         step(hipEventRecord(b->done, gs), "hipEventRecord");
     } else {
@@ -254,7 +265,7 @@ int run_stream_batch(ro_stft *h, int64_t rows)
         ro_scan_record_t *recs = h->cfg.enable_scan ? sl.d_records : nullptr;
         rc = launch_transform(h, sl.d_iq, h->stage_fmt, 0, rows, sl.d_rows, h->bins, h->stream, sl.d_tile, recs, sl.d_ln);
         if (rc == RO_OK)
-            rc = launch_tile_and_scan(h, sl.d_rows, h->bins, rows, sl.d_tile, recs, h->stream, sl.d_ln, sl.d_minmax);
+            rc = launch_tile_and_scan(h, sl.d_rows, h->bins, rows, sl.d_tile, recs, h->stream, sl.d_ln, sl.d_minmax, g_ext);
     }
     step(hipEventRecord(b->k1, h->stream), "hipEventRecord") && step(hipEventRecord(sl.computed, h->stream), "hipEventRecord");
     // download (s_out): only the columns somebody asked for travel -- the tile when one is configured
@@ -279,6 +290,7 @@ int run_stream_batch(ro_stft *h, int64_t rows)
         if (h->cfg.enable_scan)
             step(hipMemcpyAsync(b->records, sl.d_records, (size_t)rows * sizeof(ro_scan_record_t), hipMemcpyDeviceToHost,
                                 h->s_out), "download");
+        if (g_ext) step(hipMemcpyAsync(b->extra, sl.d_extra, ext_bytes, hipMemcpyDeviceToHost, h->s_out), "download");
         if (h->cfg.tile_ln) {
             step(hipMemcpyAsync(b->ln, sl.d_ln, (size_t)rows * h->out_cols * sizeof(float), hipMemcpyDeviceToHost, h->s_out),
                  "download");
@@ -340,6 +352,7 @@ void destroy_batch(Batch *b)
     if (b->ln) (void)hipHostFree(b->ln);
     if (b->minmax) (void)hipHostFree(b->minmax);
     if (b->records) (void)hipHostFree(b->records);
+    if (b->extra) (void)hipHostFree(b->extra);
     if (b->done) (void)hipEventDestroy(b->done);
     if (b->k0) (void)hipEventDestroy(b->k0);
     if (b->k1) (void)hipEventDestroy(b->k1);
@@ -355,6 +368,7 @@ void free_stream_slots(ro_stft *h)
         if (sl.d_ln) (void)hipFree(sl.d_ln);
         if (sl.d_minmax) (void)hipFree(sl.d_minmax);
         if (sl.d_records) (void)hipFree(sl.d_records);
+        if (sl.d_extra) (void)hipFree(sl.d_extra);
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
         if (sl.computed) (void)hipEventDestroy(sl.computed);
@@ -511,10 +525,13 @@ extern "C" int ro_stft_flush(ro_stft_t *h, int64_t *rows_ready)
     return RO_OK;
 }
 
-extern "C" int ro_stft_fetch(ro_stft_t *h, int64_t max_rows, int first_col, int cols, float *rows_out,
-                             ro_scan_record_t *records_out, int64_t *first_row_index, int64_t *rows_got)
+// ro_stft_fetch and ro_stft_fetch_sets (extra_out: the extra band sets' records, max_rows x extra_count)
+static int fetch_rows(ro_stft_t *h, int64_t max_rows, int first_col, int cols, float *rows_out, ro_scan_record_t *records_out,
+                      ro_scan_record_t *extra_out, int64_t *first_row_index, int64_t *rows_got)
 {
     if (!h || !rows_got) return fail(RO_ERR_INVALID, "null argument");
+    if (extra_out && h->extra_count == 0)
+        return fail(RO_ERR_STATE, "extra records requested but no extra band sets are set (ro_stft_set_extra_bands)");
     if (max_rows < 0) return fail(RO_ERR_INVALID, "negative max_rows");
     if (rows_out && (first_col < h->out_first || cols <= 0 || first_col + cols > h->out_first + h->out_cols))
         return fail(RO_ERR_INVALID, "columns [%d,+%d) outside [%d,+%d) -- what this handle brings to the host%s",
@@ -538,6 +555,9 @@ extern "C" int ro_stft_fetch(ro_stft_t *h, int64_t max_rows, int first_col, int 
             }
             if (records_out) records_out[got + r] = b->records[(size_t)(b->consumed + r)];
         }
+        if (extra_out)
+            std::memcpy(extra_out + (size_t)got * h->extra_count, b->extra + (size_t)b->consumed * h->extra_count,
+                        sizeof(ro_scan_record_t) * (size_t)take * h->extra_count);
         b->consumed += take;
         got += take;
         if (b->consumed == b->rows) {
@@ -551,6 +571,57 @@ extern "C" int ro_stft_fetch(ro_stft_t *h, int64_t max_rows, int first_col, int 
     h->timing.fetch_calls += 1;
     h->fetch_ms_sum += dt;
     h->timing.fetch_ms_max = std::max(h->timing.fetch_ms_max, dt);
+    return RO_OK;
+}
+
+extern "C" int ro_stft_fetch(ro_stft_t *h, int64_t max_rows, int first_col, int cols, float *rows_out,
+                             ro_scan_record_t *records_out, int64_t *first_row_index, int64_t *rows_got)
+{
+    return fetch_rows(h, max_rows, first_col, cols, rows_out, records_out, nullptr, first_row_index, rows_got);
+}
+
+extern "C" int ro_stft_fetch_sets(ro_stft_t *h, int64_t max_rows, int first_col, int cols, float *rows_out,
+                                  ro_scan_record_t *records_out, ro_scan_record_t *extra_out, int64_t *first_row_index,
+                                  int64_t *rows_got)
+{
+    return fetch_rows(h, max_rows, first_col, cols, rows_out, records_out, extra_out, first_row_index, rows_got);
+}
+
+// The extra band sets of a handle (several detectors on one waterfall, src/WaterfallBackend.cpp:534-536,
+// src/BolidRecorder.cpp:84-104).  Everything sized by their number starts over: the slots' record blocks, the pinned
+// batches, and the slots' captured graphs, whose scan_sets_kernel node holds the bands in its arguments.
+extern "C" int ro_stft_set_extra_bands(ro_stft_t *h, const ro_bands_t *sets, int count)
+{
+    if (!h) return fail(RO_ERR_INVALID, "null handle");
+    if (count < 0 || count > RO_MAX_EXTRA_BANDS)
+        return fail(RO_ERR_INVALID, "%d extra band sets: a handle takes 0 ... %d", count, RO_MAX_EXTRA_BANDS);
+    if (count > 0 && !sets) return fail(RO_ERR_INVALID, "null band sets");
+    if (count > 0 && !h->cfg.enable_scan)
+        return fail(RO_ERR_STATE, "extra band sets need a primary set (enable_scan / ro_stft_set_bands)");
+    if (!h->ready.empty() || h->staged_have > 0)
+        return fail(RO_ERR_STATE, "the extra band sets can only change on an idle stream (after create or ro_stft_reset)");
+    for (int i = 0; i < count; ++i)
+        if (const int rc = check_bands(h, sets[i])) {
+            const std::string why = last_error_text();
+            return fail(rc, "extra band set %d: %s", i, why.c_str());
+        }
+    HIP_TRY(hipSetDevice(h->device));
+    // nothing of the handle's may still be running on the old blocks
+    if (h->s_in) HIP_TRY(hipStreamSynchronize(h->s_in));
+    if (h->stream) HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->s_out) HIP_TRY(hipStreamSynchronize(h->s_out));
+    for (auto &sl : h->slot) {
+        if (sl.gstream) HIP_TRY(hipStreamSynchronize(sl.gstream));
+        if (sl.gexec) { (void)hipGraphExecDestroy(sl.gexec); sl.gexec = nullptr; }
+        if (sl.d_extra) { (void)hipFree(sl.d_extra); sl.d_extra = nullptr; }
+    }
+    while (!h->batch_pool.empty()) { destroy_batch(h->batch_pool.back()); h->batch_pool.pop_back(); }
+    h->extra_count = 0;
+    if (h->slots_ready && count > 0)          // (else the first push allocates them with the other streaming buffers)
+        for (auto &sl : h->slot)
+            HIP_TRY(hipMalloc(&sl.d_extra, (size_t)h->batch_rows * count * sizeof(ro_scan_record_t)));
+    for (int i = 0; i < count; ++i) h->extra[i] = sets[i];
+    h->extra_count = count;
     return RO_OK;
 }
 

@@ -65,7 +65,7 @@ bool BolidRecorder::scanBands(ro_bands_t *b) const
 void BolidRecorder::update()
 {
     if (!backend_->scanEnabled()) return;
-    const ro_scan_record_t &s = backend_->currentScan();             // n, p, a of :124-132
+    const ro_scan_record_t &s = backend_->currentScan(scanSlot_);    // n, p, a of :124-132, over THIS detector's bands
     const float n = s.noise, a = s.average;
     const int   p = s.peak;
     const float peakFq = backend_->binToFrequency(lowDetectBin_ + p);   // :133

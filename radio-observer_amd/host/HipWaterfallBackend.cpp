@@ -63,10 +63,27 @@ bool WaterfallBase::beginStream(const StreamInfo &info, ro_bands_t *bands)
         if (cfg_.keep_raw) rawBuffer_.resize(2, 1024 * 1024, want);
     }
     for (Recorder *r : recorders_) r->start();                                   // :591-593
-    bool any = false;
-    for (Recorder *r : recorders_)
-        if (!any && r->scanBands(bands)) any = true;
-    return any;
+    // one band set per recorder that wants one (src/WaterfallBackend.cpp:534-536 calls every recorder for every row,
+    // src/BolidRecorder.cpp:84-104 gives each its own bands): the first is the handle's primary set, the others its
+    // extra sets, in this order
+    int sets = 0;
+    extraBands_.clear();
+    streamError_.clear();
+    for (Recorder *r : recorders_) {
+        ro_bands_t b;
+        if (!r->scanBands(&b)) continue;
+        if (sets == MAX_SCAN_SETS) {
+            streamError_ = "waterfall: more than " + std::to_string(MAX_SCAN_SETS) + " detectors on one stream (a handle scans "
+                           "one primary band set and RO_MAX_EXTRA_BANDS = " + std::to_string(RO_MAX_EXTRA_BANDS) + " extra ones)";
+            extraBands_.clear();
+            return false;
+        }
+        r->setScanSlot(sets);
+        if (sets == 0) *bands = b;
+        else extraBands_.push_back(b);
+        ++sets;
+    }
+    return sets > 0;
 }
 
 CsvLog *WaterfallBase::getMetadataFile()
@@ -108,6 +125,12 @@ void WaterfallBase::finishStream()
 // WaterfallBackend::processFFT minus the arithmetic (src/WaterfallBackend.cpp:485-541)
 void WaterfallBase::processRow(const float *row, const ro_scan_record_t *scan, DataInfo info, int rawMark)
 {
+    processRow(row, scan, nullptr, 0, info, rawMark);
+}
+
+void WaterfallBase::processRow(const float *row, const ro_scan_record_t *scan, const ro_scan_record_t *extra, int extraCount,
+                               DataInfo info, int rawMark)
+{
     {
         // the ring's bookkeeping is shared with the recorders' worker threads (reservations, size); the row itself is
         // written into a slot no queued snapshot covers
@@ -116,7 +139,8 @@ void WaterfallBase::processRow(const float *row, const ro_scan_record_t *scan, D
         if (row) std::memcpy(dst, row, sizeof(float) * (size_t)bins_);           // (nullptr: already there -- the row sink)
         rawHandles_[buffer_.mark()] = RawDataHandle(rawMark, info.timeOffset);   // :507 (one slot ahead)
     }
-    if (scan) currentScan_ = *scan;
+    if (scan) currentScan_[0] = *scan;
+    for (int s = 0; extra && s < extraCount && 1 + s < MAX_SCAN_SETS; ++s) currentScan_[1 + s] = extra[s];
     rowsDelivered_++;
     if (keepLog_) rowLog_.push_back(RowInfo{info.offset, info.timeOffset, rawMark});
     for (Recorder *r : recorders_) r->update();                                  // :534-536
@@ -203,6 +227,12 @@ void HipWaterfallBackend::startStream(StreamInfo info)
     ro_stft_config_t c;
     std::memset(&c, 0, sizeof(c));
     scanEnabled_ = beginStream(info, &c.bands);
+    if (!streamError_.empty()) {
+        // more detectors than a handle has band sets: no handle, no rows -- never one detector on another's record
+        lastError_ = streamError_;
+        std::fprintf(stderr, "HipWaterfallBackend: %s\n", lastError_.c_str());
+        return;
+    }
     c.struct_size = sizeof(c);
     c.bins = bins_;
     c.overlap = overlap_;
@@ -244,6 +274,14 @@ void HipWaterfallBackend::startStream(StreamInfo info)
         // the reference logs and carries on (LOG_ERROR + return); so does this: no rows will come
         lastError_ = ro_last_error();
         std::fprintf(stderr, "HipWaterfallBackend: %s\n", lastError_.c_str());
+        stft_ = nullptr;
+        return;
+    }
+    // every further detector's band set (src/BolidRecorder.cpp:84-104) as an extra set of the handle: one record each per row
+    if (!extraBands_.empty() && ro_stft_set_extra_bands(stft_, extraBands_.data(), (int)extraBands_.size()) != RO_OK) {
+        lastError_ = ro_last_error();
+        std::fprintf(stderr, "HipWaterfallBackend: %s\n", lastError_.c_str());
+        ro_stft_destroy(stft_);
         stft_ = nullptr;
         return;
     }
@@ -361,6 +399,8 @@ void HipWaterfallBackend::drain(bool flush, bool wait)
     const int64_t CH = 64;
     if (!rowSink_) fetchRows_.resize((size_t)CH * bins_);
     fetchRecs_.resize((size_t)CH);
+    const int nExtra = scanEnabled_ ? (int)extraBands_.size() : 0;
+    fetchExtra_.resize((size_t)CH * (size_t)nExtra);
     // Between two process() calls only what has FINISHED on the device is handed over: the batch this call has just
     // launched stays in flight under the recorders' work and under the next call's staging (two batches overlap: one
     // downloading, one uploading / transforming), and its rows reach the recorders with the next call.  At the end of
@@ -386,8 +426,12 @@ void HipWaterfallBackend::drain(bool flush, bool wait)
             budget = launched - rowsFetched_ - (int64_t)maxOutstanding_ * batchRows_;
         }
         const int64_t want = budget < 0 ? CH : std::min<int64_t>(CH, budget);
-        if (ro_stft_fetch(stft_, want, 0, bins_, rowSink_ ? nullptr : fetchRows_.data(), scanEnabled_ ? fetchRecs_.data() : nullptr,
-                          &first, &got) != RO_OK) {
+        const int frc = nExtra > 0
+            ? ro_stft_fetch_sets(stft_, want, 0, bins_, rowSink_ ? nullptr : fetchRows_.data(), fetchRecs_.data(),
+                                 fetchExtra_.data(), &first, &got)
+            : ro_stft_fetch(stft_, want, 0, bins_, rowSink_ ? nullptr : fetchRows_.data(),
+                            scanEnabled_ ? fetchRecs_.data() : nullptr, &first, &got);
+        if (frc != RO_OK) {
             lastError_ = ro_last_error();
             return;
         }
@@ -405,8 +449,8 @@ void HipWaterfallBackend::drain(bool flush, bool wait)
             // there is no overlap to move.
             const int64_t s = (overlap_ > 0 ? (r + 1) : r) * (int64_t)hop_;
             const int rawMark = (int)((s + 1) % rawCapacity_);
-            processRow(rowSink_ ? nullptr : &fetchRows_[(size_t)i * bins_], scanEnabled_ ? &fetchRecs_[(size_t)i] : nullptr, di,
-                       rawMark);
+            processRow(rowSink_ ? nullptr : &fetchRows_[(size_t)i * bins_], scanEnabled_ ? &fetchRecs_[(size_t)i] : nullptr,
+                       nExtra > 0 ? &fetchExtra_[(size_t)i * (size_t)nExtra] : nullptr, nExtra, di, rawMark);
         }
     }
 }

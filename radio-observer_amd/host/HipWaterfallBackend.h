@@ -59,8 +59,13 @@ public:
     virtual void update() = 0;
     // the scan bands a recorder wants computed on the GPU for every row (none by default)
     virtual bool scanBands(ro_bands_t *) const { return false; }
+    // which of the row's scan records is this recorder's: 0 = the handle's primary band set, 1 + s = extra set s.  The
+    // backend hands the slots out in addRecorder order when a stream begins (WaterfallBase::beginStream).
+    void setScanSlot(int slot) { scanSlot_ = slot; }
+    int  scanSlot() const { return scanSlot_; }
 
 protected:
+    int                         scanSlot_ = 0;
     WaterfallBase              *backend_;
     RingBuffer2D<float>        *buffer_ = nullptr;
     RingBuffer2D<float>        *rawBuffer_ = nullptr;     // raw I/Q, 2 floats per sample (src/FFTBackend.h:99)
@@ -135,7 +140,14 @@ public:
     void setClock(WFTime fixed) { fixedClock_ = fixed; useFixedClock_ = true; }
 
     // ---- what the row being delivered looks like (valid inside Recorder::update())
-    const ro_scan_record_t &currentScan() const { return currentScan_; }
+    // one record per detector: slot 0 is the primary band set's, slot 1 + s extra set s's (Recorder::scanSlot)
+    static constexpr int MAX_SCAN_SETS = 1 + RO_MAX_EXTRA_BANDS;
+    const ro_scan_record_t &currentScan() const { return currentScan_[0]; }
+    const ro_scan_record_t &currentScan(int slot) const { return currentScan_[slot >= 0 && slot < MAX_SCAN_SETS ? slot : 0]; }
+    // the band sets behind slots 1, 2, ... of this stream (the primary's go out through beginStream's argument)
+    const std::vector<ro_bands_t> &extraBands() const { return extraBands_; }
+    // why the stream did not begin: more detectors than a handle scans band sets for ("" when it did)
+    const std::string &streamError() const { return streamError_; }
     bool  scanEnabled() const { return scanEnabled_; }
     int64_t currentRowIndex() const { return rowsDelivered_ - 1; }   // DataInfo::offset of that row
 
@@ -151,12 +163,18 @@ public:
 
 protected:
     // src/WaterfallBackend.cpp:573-594 (ring sizing, recorders' start()); returns the scan bands a
-    // recorder asked for through *bands (true if any)
+    // recorder asked for through *bands (true if any).  Every recorder is asked, in addRecorder order: the first that
+    // answers is the primary (*bands, slot 0), the following ones fill extraBands_ (slots 1, 2, ...), and each is told
+    // its slot.  More than MAX_SCAN_SETS of them: no scan at all, false, and streamError() says so -- each detector has
+    // its own record or none has (src/WaterfallBackend.cpp:534-536 calls every recorder with its own bands)
     bool beginStream(const StreamInfo &info, ro_bands_t *bands);
     void finishStream();                                             // :600-607
     // the reference's hook (src/FFTBackend.h:104) sees complex spectra; here the finished magnitude row
     // is handed over instead (the spectrum never leaves the GPU)
     virtual void processRow(const float *row, const ro_scan_record_t *scan, DataInfo info, int rawMark);
+    // ... with the row's records of the extra band sets: extra[s] is slot 1 + s's
+    virtual void processRow(const float *row, const ro_scan_record_t *scan, const ro_scan_record_t *extra, int extraCount,
+                            DataInfo info, int rawMark);
 
     WaterfallConfig cfg_;
     StreamInfo info_;
@@ -181,7 +199,9 @@ protected:
     int     maxOutstanding_ = 1;      // batches launched and not yet handed to the recorders (drain)
     int64_t rowsDelivered_ = 0;
     int64_t rowsFetched_ = 0;        // rows taken out of the handle's queue (== rowsDelivered_ between calls)
-    ro_scan_record_t currentScan_{};
+    ro_scan_record_t currentScan_[MAX_SCAN_SETS] = {};
+    std::vector<ro_bands_t> extraBands_;
+    std::string streamError_;
     std::vector<RowInfo> rowLog_;
     bool keepLog_ = false;
 };
@@ -191,7 +211,13 @@ protected:
 class ManualWaterfall : public WaterfallBase {
 public:
     explicit ManualWaterfall(const WaterfallConfig &cfg) : WaterfallBase(cfg) {}
-    void startStream(const StreamInfo &info) { ro_bands_t b; scanEnabled_ = beginStream(info, &b); }
+    // false: more detectors than band sets (streamError() has the text; no recorder sees a scan record then)
+    bool startStream(const StreamInfo &info)
+    {
+        ro_bands_t b;
+        scanEnabled_ = beginStream(info, &b);
+        return streamError_.empty();
+    }
     void pushSamples(const Complex *data, size_t n) { pushRaw(data, n); }
     void pushRow(const float *row, const ro_scan_record_t *scan, WFTime time, int rawMark)
     {
@@ -199,6 +225,15 @@ public:
         di.offset = (SampleCount)rowsDelivered_;
         di.timeOffset = time;
         processRow(row, scan, di, rawMark);
+    }
+    // ... every detector its own record: `scan` is slot 0's, extra[0 .. extraCount) those of slots 1, 2, ...
+    void pushRow(const float *row, const ro_scan_record_t *scan, const ro_scan_record_t *extra, int extraCount, WFTime time,
+                 int rawMark)
+    {
+        DataInfo di;
+        di.offset = (SampleCount)rowsDelivered_;
+        di.timeOffset = time;
+        processRow(row, scan, extra, extraCount, di, rawMark);
     }
     void endStream() { finishStream(); }
 };
@@ -233,6 +268,7 @@ private:
     std::deque<WFTime> rowTimes_;    // time of the first sample of rows not yet delivered
     std::vector<float> fetchRows_;
     std::vector<ro_scan_record_t> fetchRecs_;
+    std::vector<ro_scan_record_t> fetchExtra_;   // CH x extraBands_.size(): the extra band sets' records (ro_stft_fetch_sets)
 };
 
 }  // namespace ro
