@@ -65,7 +65,11 @@ enum { RO_IQ_F32 = 0, RO_IQ_I16 = 1, RO_IQ_F64 = 2 };
 enum { RO_PRECISION_F32 = 0, RO_PRECISION_F64 = 1 };
 
 /* bin ranges of BolidRecorder::start (src/BolidRecorder.cpp:84-102), in
- * fft-shifted row columns. */
+ * fft-shifted row columns.
+ * Both bands lie inside [0, bins); a detect band may touch column 0 or column bins.  average() then reads avg_bins
+ * columns from low_detect + peak - avg_bins / 2, and that window can leave the row: columns outside [0, bins)
+ * count as 0, and the sum is still divided by avg_bins (the reference reads out of bounds there, src/BolidRecorder.cpp
+ * :126-132; tests/test_gpu_scan_edges.py pins this on every kernel that scans). */
 typedef struct ro_bands {
     int32_t low_noise;     /* lowNoiseBin_      */
     int32_t noise_width;   /* noiseWidth_       */
