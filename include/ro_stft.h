@@ -47,7 +47,8 @@ enum { RO_WINDOW_NUTTALL = 0, RO_WINDOW_HANN = 1, RO_WINDOW_CUSTOM = 2 };
  *       229-232) and also take them device-resident; every other handle accepts
  *       them through ro_stft_push only and narrows them to float32 while staging
  *       (lossless for every frontend the reference has: int16 WAV, float32 raw /
- *       JACK). */
+ *       JACK).  ro_stft_band_resident takes them device-resident and un-narrowed
+ *       on RO_PRECISION_F64 handles of 131072 ... 1048576 bins. */
 enum { RO_IQ_F32 = 0, RO_IQ_I16 = 1, RO_IQ_F64 = 2 };
 
 /* arithmetic of the transform.
@@ -314,6 +315,12 @@ int ro_stft_ln_tile_resident(ro_stft_t *h, const float *d_rows, int64_t row_stri
  * 16384 ... 1048576, 1 <= cols <= 1024.  Pure host. */
 int ro_stft_band_supported(int bins, int cols);
 
+/* The same question for a handle of the given precision.  RO_PRECISION_F32: ro_stft_band_supported.  RO_PRECISION_F64
+ * (the reference's own arithmetic, src/FFTBackend.cpp:229-236, src/WaterfallBackend.cpp:497-503): bins a power of two
+ * 131072 ... 1048576, 1 <= cols <= 1024 -- up to 65536 bins an FP64 handle's full row comes from registers without
+ * scratch, and the band call stays refused there.  Any other precision: 0.  Pure host. */
+int ro_stft_band_supported_precision(int bins, int cols, int precision);
+
 /* Smallest column range that holds everything the recorders read of a row: the noise band (noise(),
  * src/BolidRecorder.cpp:313-317), the detect band (peak(), :323-335) widened by what average() reads around any peak
  * (:126-132, :338-347: [low_detect - avg_bins/2, low_detect + detect_width - 1 - avg_bins/2 + avg_bins)), and, if
@@ -328,9 +335,13 @@ int ro_bands_hull(const ro_bands_t *bands, int bins, int tile_first_col, int til
  * BolidRecorder::update, src/BolidRecorder.cpp:121-132).  d_band: device, rows x band_stride floats (band_stride >=
  * cols; floats beyond cols in a row are not touched).  d_records (optional; needs enable_scan and the handle's bands,
  * with the average's margin, inside the band -- RO_ERR_INVALID otherwise): the same records
- * ro_stft_scan_resident gives on the full row.  RO_PRECISION_F32 handles, RO_IQ_F32 / RO_IQ_I16;
- * RO_ERR_UNSUPPORTED for FP64 handles, chirp-z lengths and shapes ro_stft_band_supported refuses.
- * Same float32 bar as the rows: within 1e-5 of the FULL row's maximum.  Two launches on the same input give the same
+ * ro_stft_scan_resident gives on the full row.  RO_PRECISION_F32 handles: RO_IQ_F32 / RO_IQ_I16, the float32 bar of
+ * the rows (within 1e-5 of the FULL row's maximum).  RO_PRECISION_F64 handles of 131072 ... 1048576 bins: the same
+ * columns in the reference's arithmetic (double window multiply, double transform, double sqrt, narrowed once:
+ * src/FFTBackend.cpp:229-236, src/WaterfallBackend.cpp:497-503), RO_IQ_F32 / RO_IQ_I16 / RO_IQ_F64 (un-narrowed),
+ * every bin within one float32 ulp of the reference's; d_band stays float32.
+ * RO_ERR_UNSUPPORTED for FP64 handles of up to 65536 bins, chirp-z lengths and shapes
+ * ro_stft_band_supported_precision refuses.  Two launches on the same input give the same
  * bits.  Asynchronous on `stream`; uses handle scratch, so one launch of a handle in flight at a time. */
 int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples,
                           int64_t first_row, int64_t rows, int first_col, int cols,

@@ -117,6 +117,7 @@ _EXPORTS = {
     "ro_stft_ln_tile_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ro_stft_band_supported": (C.c_int, [C.c_int, C.c_int]),
+    "ro_stft_band_supported_precision": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "ro_bands_hull": (C.c_int, [C.POINTER(Bands), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ro_stft_band_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                         C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -304,9 +305,10 @@ def bins_supported(bins):
     return bool(library().ro_bins_supported(bins))
 
 
-def band_supported(bins, cols):
-    """whether Stft.band_resident can produce `cols` columns of a `bins`-bin row -- ro_stft_band_supported"""
-    return bool(library().ro_stft_band_supported(bins, cols))
+def band_supported(bins, cols, precision=RO_PRECISION_F32):
+    """whether Stft.band_resident can produce `cols` columns of a `bins`-bin row on a handle of `precision` --
+    ro_stft_band_supported_precision (RO_PRECISION_F64: 131072 bins and above)"""
+    return bool(library().ro_stft_band_supported_precision(bins, cols, precision))
 
 
 def bands_hull(bands, bins, tile_first_col=0, tile_cols=0):

@@ -28,6 +28,7 @@
 #include "../../include/ro_stft.h"
 #include "ro_kernels.h"
 #include "ro_band.h"
+#include "ro_band_f64.h"
 #include "ro_narrow.h"
 
 // a -DRO_DIAG=1 build (tools/ab_build.sh) reads its run-time knobs (RO_BIG_FORM, RO_F64_SCRATCH_MB) from the environment
@@ -237,6 +238,13 @@ struct ro_stft {
     float2 *d_band_t2 = nullptr;       // [slabs][cols]: exp(-2 pi i (slab a) k / bins)
     float2 *d_band_part = nullptr;
     size_t  band_part_bytes = 0;
+    // ... on RO_PRECISION_F64 handles of 131072 bins and above (ro_band_f64.hip): the same three tables and the partial sums
+    // in double (band_first / band_cols say which band they belong to; a handle has one precision, so one set is in use)
+    double2 *d_band64_tw = nullptr;
+    double2 *d_band64_t1 = nullptr;
+    double2 *d_band64_t2 = nullptr;
+    double2 *d_band64_part = nullptr;
+    size_t   band64_part_bytes = 0;
 
     // strict precision (RO_PRECISION_F64): double twiddle table + two complex-double scratch blocks
     bool     f64 = false;

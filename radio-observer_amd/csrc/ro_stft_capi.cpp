@@ -784,6 +784,10 @@ extern "C" int ro_stft_destroy(ro_stft_t *h)
     if (h->d_band_t1) (void)hipFree(h->d_band_t1);
     if (h->d_band_t2) (void)hipFree(h->d_band_t2);
     if (h->d_band_part) (void)hipFree(h->d_band_part);
+    if (h->d_band64_tw) (void)hipFree(h->d_band64_tw);
+    if (h->d_band64_t1) (void)hipFree(h->d_band64_t1);
+    if (h->d_band64_t2) (void)hipFree(h->d_band64_t2);
+    if (h->d_band64_part) (void)hipFree(h->d_band64_part);
     for (int i = 0; i < 2; ++i)
         if (h->d_scratch_d[i]) (void)hipFree(h->d_scratch_d[i]);
     if (h->d_f64_ring) (void)hipFree(h->d_f64_ring);
@@ -1016,6 +1020,14 @@ extern "C" int ro_stft_band_supported(int bins, int cols)
     return ro::band_plan(bins, cols, p) ? 1 : 0;
 }
 
+extern "C" int ro_stft_band_supported_precision(int bins, int cols, int precision)
+{
+    if (precision == RO_PRECISION_F32) return ro_stft_band_supported(bins, cols);
+    if (precision != RO_PRECISION_F64) return 0;
+    ro::Band64Plan p;
+    return ro::band64_plan(bins, cols, p) ? 1 : 0;
+}
+
 extern "C" int ro_bands_hull(const ro_bands_t *b, int bins, int tile_first_col, int tile_cols, int *first_col, int *cols)
 {
     if (!b || !first_col || !cols) return fail(RO_ERR_INVALID, "ro_bands_hull: null argument");
@@ -1079,6 +1091,44 @@ int ensure_band_tables(ro_stft *h, const ro::BandPlan &p, int first_col, int col
     return RO_OK;
 }
 
+// exp(-2 pi i e / n) for an exactly reduced integer phase e in [0, n), evaluated in long double and rounded once
+double2 unit_root_d(int64_t e, int64_t n)
+{
+    const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)e / (long double)n;
+    return make_double2((double)cosl(ang), (double)sinl(ang));
+}
+
+// ... the same tables in double, for the FP64 band kernels (ro_band_f64.hip)
+int ensure_band64_tables(ro_stft *h, const ro::Band64Plan &p, int first_col, int cols)
+{
+    if (h->band_first == first_col && h->band_cols == cols) return RO_OK;
+    if (h->d_band64_t1) {                               // an earlier launch may still be reading the old tables
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(h->d_band64_tw); h->d_band64_tw = nullptr;
+        (void)hipFree(h->d_band64_t1); h->d_band64_t1 = nullptr;
+        (void)hipFree(h->d_band64_t2); h->d_band64_t2 = nullptr;
+        h->band_first = -1;
+        h->band_cols = 0;
+    }
+    const int64_t n = h->bins;
+    std::vector<double2> tw((size_t)p.m), t1((size_t)cols * p.a), t2((size_t)p.slabs * cols);
+    for (int j = 0; j < p.m; ++j) tw[(size_t)j] = unit_root_d(j, p.m);
+    for (int j = 0; j < cols; ++j) {
+        const int64_t k = ((int64_t)first_col + j + n / 2) % n;
+        for (int t = 0; t < p.a; ++t) t1[(size_t)j * p.a + t] = unit_root_d((t * k) % n, n);
+        for (int s = 0; s < p.slabs; ++s) t2[(size_t)s * cols + j] = unit_root_d(((int64_t)s * p.a * k) % n, n);
+    }
+    HIP_TRY(hipMalloc(&h->d_band64_tw, sizeof(double2) * tw.size()));
+    HIP_TRY(hipMalloc(&h->d_band64_t1, sizeof(double2) * t1.size()));
+    HIP_TRY(hipMalloc(&h->d_band64_t2, sizeof(double2) * t2.size()));
+    HIP_TRY(hipMemcpy(h->d_band64_tw, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_band64_t1, t1.data(), sizeof(double2) * t1.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_band64_t2, t2.data(), sizeof(double2) * t2.size(), hipMemcpyHostToDevice));
+    h->band_first = first_col;
+    h->band_cols = cols;
+    return RO_OK;
+}
+
 }  // namespace
 
 extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
@@ -1086,15 +1136,20 @@ extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format,
                                      ro_scan_record_t *d_records, void *stream)
 {
     if (!h) return fail(RO_ERR_INVALID, "null handle");
-    if (h->f64) return fail(RO_ERR_UNSUPPORTED, "the band-only transform is float32: not for RO_PRECISION_F64 handles");
     if (h->czt) return fail(RO_ERR_UNSUPPORTED, "the band-only transform needs power-of-two bins (got %d)", h->bins);
-    if (format == RO_IQ_F64) return fail(RO_ERR_UNSUPPORTED, "the band-only transform takes RO_IQ_F32 or RO_IQ_I16 samples");
-    if (format != RO_IQ_F32 && format != RO_IQ_I16)
-        return fail(RO_ERR_INVALID, "resident input must be RO_IQ_F32 or RO_IQ_I16 (got %d)", format);
-    ro::BandPlan p;
-    if (!ro::band_plan(h->bins, cols, p))
-        return fail(RO_ERR_UNSUPPORTED, "no band kernel for %d columns of %d bins (bins a power of two 16384 ... 1048576, "
-                                        "1 ... 1024 columns)", cols, h->bins);
+    if (h->f64 && h->bins < 131072)
+        return fail(RO_ERR_UNSUPPORTED, "the band-only transform of RO_PRECISION_F64 handles starts at 131072 bins (got %d): "
+                                        "up to 65536 the full row comes from registers without scratch", h->bins);
+    if (format == RO_IQ_F64 && !h->f64)
+        return fail(RO_ERR_UNSUPPORTED, "the band-only transform takes RO_IQ_F32 or RO_IQ_I16 samples "
+                                        "(RO_IQ_F64 on RO_PRECISION_F64 handles of 131072 bins and above)");
+    if (format != RO_IQ_F32 && format != RO_IQ_I16 && format != RO_IQ_F64)
+        return fail(RO_ERR_INVALID, "resident input must be RO_IQ_F32, RO_IQ_I16 or RO_IQ_F64 (got %d)", format);
+    ro::BandPlan p{};
+    ro::Band64Plan p64{};
+    if (h->f64 ? !ro::band64_plan(h->bins, cols, p64) : !ro::band_plan(h->bins, cols, p))
+        return fail(RO_ERR_UNSUPPORTED, "no band kernel for %d columns of %d bins (bins a power of two %d ... 1048576, "
+                                        "1 ... 1024 columns)", cols, h->bins, h->f64 ? 131072 : 16384);
     if (first_col < 0 || (int64_t)first_col + cols > h->bins)
         return fail(RO_ERR_INVALID, "band [%d,+%d) outside [0,%d)", first_col, cols, h->bins);
     if (band_stride < cols) return fail(RO_ERR_INVALID, "band_stride %lld < cols %d", (long long)band_stride, cols);
@@ -1125,6 +1180,47 @@ extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format,
     if (rows > (int64_t)0x0fffffff) return fail(RO_ERR_INVALID, "too many rows in one launch");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
+    if (h->f64) {
+        int rc = ensure_band64_tables(h, p64, first_col, cols);
+        if (rc != RO_OK) return rc;
+        // the partial sums, chunked by rows exactly like the float32 ones below
+        const size_t row_bytes = (size_t)p64.slabs * cols * sizeof(double2);
+        const int64_t chunk = std::min<int64_t>(std::min<int64_t>(rows, 65535),
+                                                std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / row_bytes)));
+        if ((size_t)chunk * row_bytes > h->band64_part_bytes) {
+            if (h->d_band64_part) {                     // (an earlier launch may still be using the old block)
+                HIP_TRY(hipDeviceSynchronize());
+                HIP_TRY(hipFree(h->d_band64_part));
+                h->d_band64_part = nullptr;
+                h->band64_part_bytes = 0;
+            }
+            HIP_TRY(hipMalloc(&h->d_band64_part, (size_t)chunk * row_bytes));
+            h->band64_part_bytes = (size_t)chunk * row_bytes;
+        }
+        for (int64_t done = 0; done < rows; done += chunk) {
+            ro::Band64Args b{};
+            b.iq = d_iq;
+            b.window = h->d_window;
+            b.tw = h->d_band64_tw;
+            b.t1 = h->d_band64_t1;
+            b.t2 = h->d_band64_t2;
+            b.part = h->d_band64_part;
+            b.band_out = d_band + done * band_stride;
+            b.first_row = first_row + done;
+            b.rows = std::min(chunk, rows - done);
+            b.band_stride = band_stride;
+            b.hop = h->hop;
+            b.bins = h->bins;
+            b.first_col = first_col;
+            b.cols = cols;
+            b.gain = (double)h->cfg.iq_gain;
+            HIP_TRY(ro::launch_band64(p64, format, b, s));
+        }
+        if (d_records) HIP_TRY(ro::launch_scan(sc, s));
+        h->stat_launches += 1;
+        h->stat_rows += rows;
+        return RO_OK;
+    }
     int rc = ensure_band_tables(h, p, first_col, cols);
     if (rc != RO_OK) return rc;
     // the partial sums: rows per chunk like the large transforms' scratch, 256 MiB at the most, one grid of <= 65535 rows

@@ -12,7 +12,12 @@ Prints, per shape: rows/s of each leg with the spread of the five repeats, the r
 the band's algorithmic bytes (hop x 8 + cols x 4 per row) make in (b), and the worst parity figure of both legs on the
 first 8 rows (max |x - oracle| / max of the full oracle row).
 
-    python tools/band/bench_band.py [--window 0.5] [--repeats 5]
+    python tools/band/bench_band.py [--window 0.5] [--repeats 5] [--precision f32|f64]
+
+--precision f64: both legs on an RO_PRECISION_F64 handle, where (a) with tile = band is the only other way to serve the
+consumer in the reference's arithmetic.  Shapes: Ionozor's doppler configuration as above, and 131072 / 98304, 2048 rows,
+the 777-column hull of Bolidozor's bands at that size, with records.  The parity figure becomes per-bin:
+max |x - oracle| / oracle over the band's bins of the first 8 rows.
 """
 import argparse
 import importlib
@@ -62,7 +67,7 @@ def timed(torch, launch, window_s):
     return total / iters, total
 
 
-def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, args):
+def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, args, f64=False):
     hop = bins - overlap
     first_col, cols = band
     samples = (rows - 1) * hop + bins
@@ -73,7 +78,8 @@ def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, a
     rec_a = torch.zeros((rows, 3), dtype=torch.float32, device="cuda") if bands is not None else None
     rec_b = torch.zeros((rows, 3), dtype=torch.float32, device="cuda") if bands is not None else None
     stream = torch.cuda.current_stream().cuda_stream
-    with ro.Stft(bins=bins, overlap=overlap, sample_rate=fs, bands=bands, tile=tile) as st:
+    kw = {"precision": ro.RO_PRECISION_F64} if f64 else {}
+    with ro.Stft(bins=bins, overlap=overlap, sample_rate=fs, bands=bands, tile=tile, **kw) as st:
         def leg_a():
             st.run_resident(iq, ro.RO_IQ_F32, samples, 0, rows, d_rows, d_tile=d_tile, d_records=rec_a, stream=stream)
 
@@ -97,6 +103,10 @@ def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, a
     ref = want.max(axis=1)
     err_a = (np.abs(d_tile[:n8].cpu().numpy() - want[:, tile[0]:tile[0] + tile[1]]).max(axis=1) / ref).max()
     err_b = (np.abs(d_band[:n8].cpu().numpy() - want[:, first_col:first_col + cols]).max(axis=1) / ref).max()
+    if f64:                                                             # per bin, on the band's bins
+        wa, wb = want[:, tile[0]:tile[0] + tile[1]], want[:, first_col:first_col + cols]
+        err_a = (np.abs(d_tile[:n8].cpu().numpy() - wa) / wa).max()
+        err_b = (np.abs(d_band[:n8].cpu().numpy() - wb) / wb).max()
     same_peaks = ""
     if bands is not None:
         pa = rec_a.cpu().numpy().view(ro.capi.SCAN_DTYPE)["peak"].reshape(-1)
@@ -114,8 +124,29 @@ def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, a
     print("  b / a = %.2f   (slowest b / fastest a = %.2f)" % (ratio, tb.min() / ta.max()))
     print("  (b) algorithmic bytes %d per row: %.1f GB/s = %.3f of the %.0f GB/s HBM peak" %
           (alg, alg * np.median(tb) / 1e9, alg * np.median(tb) / 1e9 / HBM_PEAK_GBS, HBM_PEAK_GBS))
-    print("  parity on the first %d rows, max err / full row max: (a) %.2e  (b) %.2e%s" % (n8, err_a, err_b, same_peaks))
+    print("  parity on the first %d rows, max err / %s: (a) %.2e  (b) %.2e%s" %
+          (n8, "oracle, per bin" if f64 else "full row max", err_a, err_b, same_peaks))
     return tb.min() > ta.max()
+
+
+def main_f64(torch, ro, oracle, args):
+    ok = True
+    fs = 96000
+    # Ionozor.json:27-28, the doppler recorder's 40 Hz around 10.6 kHz: no scan
+    bins, overlap = 524288, 262144
+    band = (ro.frequency_to_bin(bins, fs, 10580.0), 218)
+    ok &= shape(torch, ro, oracle, "Ionozor doppler (FP64)", bins, overlap, fs, max(8, int(512 * args.rows_scale)), None, band,
+                band, args, f64=True)
+    # Bolidozor.json:84-93's bands on a 131072-bin row: their hull is the band and the tile
+    bins, overlap = 131072, 98304
+    b = oracle.bolid_bands(bins, fs, overlap, 26450, 26550, 26000, 26300, 5, 2, 40)
+    bands = ro.Bands(low_noise=b.low_noise, noise_width=b.noise_width, low_detect=b.low_detect,
+                     detect_width=b.detect_width, avg_bins=b.avg_bins)
+    band = ro.bands_hull(bands, bins)
+    ok &= shape(torch, ro, oracle, "Bolidozor bands at 131072 (FP64)", bins, overlap, fs, max(8, int(2048 * args.rows_scale)),
+                bands, band, band, args, f64=True)
+    print("FP64 band only faster than FP64 full rows at both shapes by more than the repeats' spread: %s" % ("yes" if ok else "NO"))
+    return 0
 
 
 def main():
@@ -123,12 +154,15 @@ def main():
     ap.add_argument("--window", type=float, default=0.5, help="seconds of launches per timed leg, at least")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--rows-scale", type=float, default=1.0, help="scale both row counts (quick runs)")
+    ap.add_argument("--precision", choices=("f32", "f64"), default="f32", help="precision of the handle both legs run on")
     args = ap.parse_args()
     import torch
     ro = importlib.import_module("radio-observer_amd")
     import ro_oracle as oracle
     oracle.lib()
     ok = True
+    if args.precision == "f64":
+        return main_f64(torch, ro, oracle, args)
     # Bolidozor.json:45-46, :75-76 (snapshot columns), :84-93 (bands; avg_freq_range at its default of 40 Hz)
     bins, overlap, fs = 65536, 49152, 96000
     b = oracle.bolid_bands(bins, fs, overlap, 26450, 26550, 26000, 26300, 5, 2, 40)
