@@ -90,10 +90,8 @@ int czt_setup(ro_stft *h)
     for (int i = 0; i < M; ++i)
         bc[(size_t)i] = make_float2((float)(b[(size_t)i].real() / M), (float)(-b[(size_t)i].imag() / M));
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMalloc(&h->d_cw, sizeof(float2) * cw.size()));
-    HIP_TRY(hipMemcpy(h->d_cw, cw.data(), sizeof(float2) * cw.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&h->d_bc, sizeof(float2) * bc.size()));
-    HIP_TRY(hipMemcpy(h->d_bc, bc.data(), sizeof(float2) * bc.size(), hipMemcpyHostToDevice));
+    HIP_TRY(h->d_cw.upload(cw));
+    HIP_TRY(h->d_bc.upload(bc));
     return RO_OK;
 }
 
@@ -105,9 +103,9 @@ int launch_transform_czt(ro_stft *h, const void *d_iq, int format, int64_t first
     const int M = h->czt_m;
     if (!h->d_czt_mag) {                                            // (each block on its own: a failed call can be retried)
         h->czt_rows = std::min<int64_t>(65535, std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)M * 8)));
-        if (!h->d_czt_a) HIP_TRY(hipMalloc(&h->d_czt_a, (size_t)h->czt_rows * M * sizeof(float2)));
-        if (!h->d_czt_A) HIP_TRY(hipMalloc(&h->d_czt_A, (size_t)h->czt_rows * M * sizeof(float2)));
-        HIP_TRY(hipMalloc(&h->d_czt_mag, (size_t)h->czt_rows * M * sizeof(float)));
+        if (!h->d_czt_a) HIP_TRY(h->d_czt_a.alloc((size_t)h->czt_rows * M));
+        if (!h->d_czt_A) HIP_TRY(h->d_czt_A.alloc((size_t)h->czt_rows * M));
+        HIP_TRY(h->d_czt_mag.alloc((size_t)h->czt_rows * M));
     }
     for (int64_t done = 0; done < rows; done += h->czt_rows) {
         const int64_t n = std::min(h->czt_rows, rows - done);

@@ -5,6 +5,7 @@
 //   ro_stream.cpp        push / flush / fetch: staging slots, captured graphs, the row sink
 //   ro_czt.cpp           lengths that are not a power of two (chirp-z on an inner handle)
 //   ro_stft_capi.cpp     create / destroy, the transform launches, the resident entry points
+// ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
 
@@ -30,6 +31,7 @@
 #include "ro_band.h"
 #include "ro_band_f64.h"
 #include "ro_narrow.h"
+#include "ro_owned.h"
 
 // a -DRO_DIAG=1 build (tools/ab_build.sh) reads its run-time knobs (RO_BIG_FORM, RO_F64_SCRATCH_MB) from the environment
 #if defined(RO_DIAG) && !defined(RO_DIAG_KNOBS)
@@ -37,11 +39,6 @@
 #endif
 
 // scratch of the large transforms' scratch form (the folded sub-rows between the kernels), MiB per block
-// largest bins / 16384 the one-kernel form of the large transforms is used for (see ro_stft_create)
-#ifndef RO_DIF_MAX_DEC
-#define RO_DIF_MAX_DEC 4
-#endif
-
 #ifndef RO_SPEC_SCRATCH_MB
 #define RO_SPEC_SCRATCH_MB 2048
 #endif
@@ -62,10 +59,13 @@
 // RO_PRECISION_F64_ONE_LAUNCH (ro_f64fused.hip): a ring of this many rows of 32768 bins per XCD (scaled so that the
 // ring's bytes stay the same at the other sizes), this many workgroups per CU.  4 rows is the least that keeps an XCD's
 // 32 workgroups busy, and all its L2 serves (profiles/r05_f64_one_launch.txt)
-// streaming path: sets of device + pinned staging buffers a handle rotates through (batches that can be in flight at once)
-#ifndef RO_GRAPH_TIME_EVERY
-#define RO_GRAPH_TIME_EVERY 8
+#ifndef RO_F64_RING_ROWS
+#define RO_F64_RING_ROWS 4
 #endif
+#ifndef RO_F64_WGS_PER_CU
+#define RO_F64_WGS_PER_CU 1
+#endif
+// streaming path: sets of device + pinned staging buffers a handle rotates through (batches that can be in flight at once)
 #ifndef RO_STREAM_SLOTS
 #define RO_STREAM_SLOTS 3
 #endif
@@ -73,11 +73,9 @@
 #ifndef RO_STREAM_GRAPH
 #define RO_STREAM_GRAPH 1
 #endif
-#ifndef RO_F64_RING_ROWS
-#define RO_F64_RING_ROWS 4
-#endif
-#ifndef RO_F64_WGS_PER_CU
-#define RO_F64_WGS_PER_CU 1
+// ... whose timing events go round one batch in this many (run_stream_batch has the measurement)
+#ifndef RO_GRAPH_TIME_EVERY
+#define RO_GRAPH_TIME_EVERY 8
 #endif
 
 namespace ro {
@@ -107,11 +105,11 @@ inline double now_ms()
 struct Batch {
     int64_t first_row = 0;
     int64_t rows = 0;
-    float *data = nullptr;                     // capacity_rows x out_cols, pinned
-    float *ln = nullptr;                       // capacity_rows x out_cols (tile_ln), pinned
-    float *minmax = nullptr;                   // capacity_rows x 2 (tile_ln), pinned
-    ro_scan_record_t *records = nullptr;       // capacity_rows, pinned
-    ro_scan_record_t *extra = nullptr;         // capacity_rows x extra_count (extra band sets), pinned
+    PinnedBlock<float> data;                   // capacity_rows x out_cols
+    PinnedBlock<float> ln;                     // capacity_rows x out_cols (tile_ln)
+    PinnedBlock<float> minmax;                 // capacity_rows x 2 (tile_ln)
+    PinnedBlock<ro_scan_record_t> records;     // capacity_rows
+    PinnedBlock<ro_scan_record_t> extra;       // capacity_rows x extra_count (extra band sets)
     int64_t capacity_rows = 0;
     int64_t consumed = 0;                      // rows already fetched
     hipEvent_t done = nullptr;
@@ -120,20 +118,34 @@ struct Batch {
     bool timed = true;                         // k0 / k1 were recorded around this batch's kernels
 };
 
+// the band-only transform's device state in one precision (T = float2: ro_band.hip, double2: ro_band_f64.hip): the tables
+// of the last band asked for and the slabs' partial sums between the two kernels, grown on demand
+template <typename T>
+struct BandState {
+    DeviceBlock<T> tw;                         // [m]: exp(-2 pi i j / m)
+    DeviceBlock<T> t1;                         // [cols][a]: exp(-2 pi i t k / bins)
+    DeviceBlock<T> t2;                         // [slabs][cols]: exp(-2 pi i (slab a) k / bins)
+    DeviceBlock<T> part;                       // [rows of a chunk][slabs][cols]
+    size_t part_bytes = 0;
+};
+
 }  // namespace host
 }  // namespace ro
 
 struct ro_stft {
+    template <typename T> using DeviceBlock = ro::host::DeviceBlock<T>;
+    template <typename T> using PinnedBlock = ro::host::PinnedBlock<T>;
+
     ro_stft_config_t cfg{};
     int bins = 0, overlap = 0, hop = 0;
     int device = 0;
     std::string device_name;
     std::vector<float> window;
-    float *d_window = nullptr;
-    float *d_window_k = nullptr;       // kernel-order copy (single-pass plans)
-    float *d_window_k32 = nullptr;     // ... in the order of the N = 32768 magnitude-row kernel (bins = 32768)
-    float2 *d_twiddles = nullptr;
-    float4 *d_twiddles_k = nullptr;    // packed copy for the radix-16/32 stages
+    DeviceBlock<float> d_window;
+    DeviceBlock<float> d_window_k;     // kernel-order copy (single-pass plans)
+    DeviceBlock<float> d_window_k32;   // ... in the order of the N = 32768 magnitude-row kernel (bins = 32768)
+    DeviceBlock<float2> d_twiddles;
+    DeviceBlock<float4> d_twiddles_k;  // packed copy for the radix-16/32 stages
     hipStream_t stream = nullptr;
     // extra band sets (ro_stft_set_extra_bands): scanned by ro_scan_sets.hip behind the primary's scan
     ro_bands_t extra[RO_MAX_EXTRA_BANDS] = {};
@@ -153,14 +165,14 @@ struct ro_stft {
     float  *sink = nullptr;
     int64_t sink_stride = 0, sink_cap = 0, sink_first = 0;
     struct Slot {
-        void  *d_iq = nullptr;                 // batch input  ((batch_rows-1)*hop + bins samples, 8 B each at most)
-        float *d_rows = nullptr;               // batch output (batch_rows x bins)
-        float *d_tile = nullptr;               // batch_rows x tile_cols when a tile is configured
-        float *d_ln = nullptr;                 // ... its log and the rows' min / max of it (tile_ln)
-        float *d_minmax = nullptr;
-        ro_scan_record_t *d_records = nullptr;
-        ro_scan_record_t *d_extra = nullptr;   // batch_rows x extra_count: the extra band sets' records
-        void  *h_in = nullptr;                 // pinned upload staging
+        DeviceBlock<char> d_iq;                // batch input, bytes ((batch_rows-1)*hop + bins samples, 8 or 16 B each)
+        DeviceBlock<float> d_rows;             // batch output (batch_rows x bins)
+        DeviceBlock<float> d_tile;             // batch_rows x tile_cols when a tile is configured
+        DeviceBlock<float> d_ln;               // ... its log and the rows' min / max of it (tile_ln)
+        DeviceBlock<float> d_minmax;
+        DeviceBlock<ro_scan_record_t> d_records;
+        DeviceBlock<ro_scan_record_t> d_extra; // batch_rows x extra_count: the extra band sets' records
+        PinnedBlock<char> h_in;                // pinned upload staging, bytes
         hipEvent_t uploaded = nullptr;         // H2D of this slot done (h_in reusable, kernels may start)
         hipEvent_t staging_free = nullptr;     // what the host waits for before it writes h_in again: `uploaded`, or the `done`
                                                // event of the graphed batch that last used the slot (not owned)
@@ -193,73 +205,63 @@ struct ro_stft {
     int64_t graph_batches = 0;
     int     diag_time_every = 0, diag_done_only = 0, diag_direct = 0;   // (-DRO_DIAG: tools/r5/host_calls_ab.py)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    unsigned long long *d_stamps = nullptr;    // diagnostic builds (RO_STAMPS) only
+    DeviceBlock<unsigned long long> d_stamps;  // diagnostic builds (RO_STAMPS) only
 
-    unsigned *d_ln_keys = nullptr;     // 16 pairs of min / max keys of ro_stft_ln_tile_resident, used in turn
+    DeviceBlock<unsigned> d_ln_keys;   // 16 pairs of min / max keys of ro_stft_ln_tile_resident, used in turn
     unsigned ln_calls = 0;
     // large transforms (bins > 32768 = dec x sub_bins, decimation in frequency on the N = 32768 plan; see ro_stft_create)
     bool    big = false;
     int     sub_bins = 0, dec = 0;
-    float2 *d_tw_combine = nullptr;    // [dec][sub_bins]: the rotations exp(-2 pi i q m / bins)
-    bool    dif = false;               // dec <= RO_DIF_MAX_DEC: one kernel sums the row's blocks itself (MODE 3)
-    float  *d_window_dif = nullptr;    // ... [dec][sub_bins]: window block r in the sub-plan's kernel order
-    float2 *d_dif_tw = nullptr;        // ... exp(-2 pi i j / dec)
-    float2 *d_dif_shift = nullptr;     // ... [dec][16]: the bin shift q / dec as the stages' twiddles (StftArgs::dif_shift)
-    float2 *d_spec = nullptr;          // ... the folded sub-rows, [spec_rows][dec][sub_bins] float2
-    float  *d_ones = nullptr;          // ... a window of ones (the fold has applied the real one)
+    DeviceBlock<float2> d_tw_combine;  // [dec][sub_bins]: the rotations exp(-2 pi i q m / bins)
+    bool    dif = false;               // 65536, 131072: one kernel sums the row's blocks itself (MODE 3)
+    DeviceBlock<float>  d_window_dif;  // ... [dec][sub_bins]: window block r in the sub-plan's kernel order
+    DeviceBlock<float2> d_dif_tw;      // ... exp(-2 pi i j / dec)
+    DeviceBlock<float2> d_dif_shift;   // ... [dec][16]: the bin shift q / dec as the stages' twiddles (StftArgs::dif_shift)
+    DeviceBlock<float2> d_spec;        // ... the folded sub-rows, [spec_rows][dec][sub_bins] float2
+    DeviceBlock<float>  d_ones;        // ... a window of ones (the fold has applied the real one)
     int64_t spec_rows = 0;
-    float2 *d_spec2 = nullptr;         // complex spectra of a large size: the sub-rows' spectra before they are interleaved
+    DeviceBlock<float2> d_spec2;       // complex spectra of a large size: the sub-rows' spectra before they are interleaved
     // bins = 262144, 524288: the magnitude rows as a four-step FFT (ro_fourstep.hip): column kernel, scratch, row kernel
     bool    four = false;
-    float  *d_four_window = nullptr;   // the window in the column kernel's order
-    float2 *d_four_tw_a = nullptr, *d_four_tw_b = nullptr, *d_four_tw_r = nullptr;     // ro::FourArgs
-    float  *d_four_z = nullptr;        // [four_rows][bins] complex
+    DeviceBlock<float>  d_four_window; // the window in the column kernel's order
+    DeviceBlock<float2> d_four_tw_a, d_four_tw_b, d_four_tw_r;                         // ro::FourArgs
+    DeviceBlock<float>  d_four_z;      // [four_rows][bins] complex
     int64_t four_rows = 0;
     // lengths that are not a power of two (even 258 .. 524286): Bluestein's chirp-z form on an inner handle of the
     // power-of-two length czt_m >= 2 bins - 1 (see ro::CztArgs)
     bool    czt = false;
     int     czt_m = 0;
     ro_stft *inner = nullptr;
-    float2 *d_cw = nullptr;            // [bins] window[i] * exp(-pi i i^2 / bins)
-    float2 *d_bc = nullptr;            // [czt_m] conj(FFT_M(conj(chirp), wrapped)) / czt_m
-    float2 *d_czt_a = nullptr, *d_czt_A = nullptr;     // [czt_rows][czt_m] each
-    float  *d_czt_mag = nullptr;                       // [czt_rows][czt_m]
+    DeviceBlock<float2> d_cw;          // [bins] window[i] * exp(-pi i i^2 / bins)
+    DeviceBlock<float2> d_bc;          // [czt_m] conj(FFT_M(conj(chirp), wrapped)) / czt_m
+    DeviceBlock<float2> d_czt_a, d_czt_A;              // [czt_rows][czt_m] each
+    DeviceBlock<float>  d_czt_mag;                     // [czt_rows][czt_m]
     int64_t czt_rows = 0;
 
     // tile_ln: partial min / max of the fused epilogue's two tile waves (rows x 4 floats), grown on demand
-    float  *d_ln_part = nullptr;
+    DeviceBlock<float> d_ln_part;
     int64_t ln_part_rows = 0;
 
-    // band-only transform (ro_stft_band_resident, ro_band.hip): the tables of the last band asked for, and the slabs'
-    // partial sums between its two kernels ([band_part_rows][slabs][cols] float2, grown on demand)
+    // band-only transform (ro_stft_band_resident): band_first / band_cols say which band the tables belong to; a handle has
+    // one precision, so one of the two sets is in use (band64: RO_PRECISION_F64 handles of 131072 bins and above)
     int     band_first = -1, band_cols = 0;
-    float2 *d_band_tw = nullptr;       // [m]: exp(-2 pi i j / m)
-    float2 *d_band_t1 = nullptr;       // [cols][a]: exp(-2 pi i t k / bins)
-    float2 *d_band_t2 = nullptr;       // [slabs][cols]: exp(-2 pi i (slab a) k / bins)
-    float2 *d_band_part = nullptr;
-    size_t  band_part_bytes = 0;
-    // ... on RO_PRECISION_F64 handles of 131072 bins and above (ro_band_f64.hip): the same three tables and the partial sums
-    // in double (band_first / band_cols say which band they belong to; a handle has one precision, so one set is in use)
-    double2 *d_band64_tw = nullptr;
-    double2 *d_band64_t1 = nullptr;
-    double2 *d_band64_t2 = nullptr;
-    double2 *d_band64_part = nullptr;
-    size_t   band64_part_bytes = 0;
+    ro::host::BandState<float2>  band;
+    ro::host::BandState<double2> band64;
 
     // strict precision (RO_PRECISION_F64): double twiddle table + two complex-double scratch blocks
     bool     f64 = false;
-    double2 *d_tw_f64 = nullptr;
+    DeviceBlock<double2> d_tw_f64;
     // ... bins 256 ... 65536: the row in a CU's registers, no scratch (ro_f64reg.hip); its window order and twiddle tables
     bool     f64reg = false;
-    float   *d_f64r_window = nullptr;
-    double2 *d_f64r_tw[4] = {nullptr, nullptr, nullptr, nullptr};
-    double2 *d_scratch_d[2] = {nullptr, nullptr};
+    DeviceBlock<float>   d_f64r_window;
+    DeviceBlock<double2> d_f64r_tw[4];
+    DeviceBlock<double2> d_scratch_d[2];
     int64_t  scratch_rows_d = 0;
     // (diagnostic builds, RO_F64_FUSED=1: round 5's one-launch form of the through-HBM passes, ro_f64fused.hip:
     // 8 rings of f64_ring_rows rows, the launch's control block, and its give-up word mirrored into pinned host memory)
-    double2  *d_f64_ring = nullptr;
-    unsigned *d_f64_ctl = nullptr;
-    unsigned *h_f64_err = nullptr;
+    DeviceBlock<double2>  d_f64_ring;
+    DeviceBlock<unsigned> d_f64_ctl;
+    PinnedBlock<unsigned> h_f64_err;
     int       f64_ring_rows = 0, f64_wgs_per_cu = 0;
 };
 

@@ -120,9 +120,27 @@ int ensure_big_scratch(ro_stft *h)
         h->spec_rows = std::max<int64_t>(1, ((int64_t)RO_SPEC_SCRATCH_MB << 20) / ((int64_t)h->bins * 8));
         if (h->spec_rows > 65535) h->spec_rows = 65535;
     }
-    if (!h->d_spec) HIP_TRY(hipMalloc(&h->d_spec, (size_t)h->spec_rows * h->bins * sizeof(float2)));
-    if (!h->d_spec2) HIP_TRY(hipMalloc(&h->d_spec2, (size_t)h->spec_rows * h->bins * sizeof(float2)));
+    if (!h->d_spec) HIP_TRY(h->d_spec.alloc((size_t)h->spec_rows * h->bins));
+    if (!h->d_spec2) HIP_TRY(h->d_spec2.alloc((size_t)h->spec_rows * h->bins));
     return RO_OK;
+}
+
+// what every through-HBM FP64 launch of rows [first_row, +rows) is told (the pass loop adds ns / in / out per pass)
+ro::BigArgsD make_bigd_args(const ro_stft *h, const void *d_iq, int64_t first_row, int64_t rows, float *d_rows,
+                            int64_t row_stride)
+{
+    ro::BigArgsD b{};
+    b.iq = d_iq;
+    b.window = h->d_window;
+    b.tw = h->d_tw_f64;
+    b.first_row = first_row;
+    b.rows = rows;
+    b.row_stride = row_stride;
+    b.hop = h->hop;
+    b.n = h->bins;
+    b.gain = h->cfg.iq_gain;
+    b.rows_out = d_rows;
+    return b;
 }
 
 #ifdef RO_DIAG
@@ -139,7 +157,7 @@ int launch_transform_f64_fused(ro_stft *h, const void *d_iq, int format, int64_t
         return fail(RO_ERR_HIP, "the previous RO_PRECISION_F64 launch gave up waiting for another workgroup (code %u: 1 = row "
                                 "map, 2 = ring slot still being read, 3 = row's first half not complete); its rows are incomplete", code);
     }
-    if (!h->d_f64_ring) {
+    if (!h->f64_ring_rows) {
         int ring = RO_F64_RING_ROWS * 32768 / h->bins, wgs = RO_F64_WGS_PER_CU;
 #ifdef RO_DIAG_KNOBS
         if (const char *e = getenv("RO_F64_RING_ROWS")) ring = atoi(e);
@@ -147,27 +165,39 @@ int launch_transform_f64_fused(ro_stft *h, const void *d_iq, int format, int64_t
 #endif
         h->f64_ring_rows = std::max(2, std::min(ring, ro::f64_fused_max_ring_rows()));
         h->f64_wgs_per_cu = std::max(1, std::min(wgs, 2));
-        HIP_TRY(hipMalloc(&h->d_f64_ring, (size_t)8 * h->f64_ring_rows * h->bins * sizeof(double2)));
-        HIP_TRY(hipMalloc(&h->d_f64_ctl, ro::f64_fused_ctl_bytes()));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->h_f64_err), sizeof(unsigned), hipHostMallocDefault));
+    }
+    // (each block on its own: a call after a failed one allocates what is missing and never launches without a block)
+    if (!h->d_f64_ring) HIP_TRY(h->d_f64_ring.alloc((size_t)8 * h->f64_ring_rows * h->bins));
+    if (!h->d_f64_ctl) HIP_TRY(h->d_f64_ctl.alloc(ro::f64_fused_ctl_bytes() / sizeof(unsigned)));
+    if (!h->h_f64_err) {
+        HIP_TRY(h->h_f64_err.alloc(1));
         *h->h_f64_err = 0;
     }
-    ro::BigArgsD b{};
-    b.iq = d_iq;
-    b.window = h->d_window;
-    b.tw = h->d_tw_f64;
-    b.first_row = first_row;
-    b.rows = rows;
-    b.row_stride = row_stride;
-    b.hop = h->hop;
-    b.n = h->bins;
-    b.gain = h->cfg.iq_gain;
-    b.rows_out = d_rows;
+    const ro::BigArgsD b = make_bigd_args(h, d_iq, first_row, rows, d_rows, row_stride);
     HIP_TRY(ro::launch_f64_fused(format, b, h->d_f64_ring, h->d_f64_ctl, h->f64_ring_rows, h->f64_wgs_per_cu, s));
     HIP_TRY(hipMemcpyAsync(h->h_f64_err, h->d_f64_ctl + 1, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     return RO_OK;
 }
 #endif
+
+// the register kernel's arguments (ro_f64reg.hip); out: magnitude rows, or complex spectra with r.spectra = 1
+ro::F64RegArgs make_f64reg_args(const ro_stft *h, const void *d_iq, int64_t first_row, int64_t rows, float *out, int64_t stride)
+{
+    ro::F64RegArgs r{};
+    r.iq = d_iq;
+    r.window_k = h->d_f64r_window;
+    r.tw0 = h->d_f64r_tw[0];
+    r.tw1 = h->d_f64r_tw[1];
+    r.tw2 = h->d_f64r_tw[2];
+    r.tw3 = h->d_f64r_tw[3];
+    r.rows_out = out;
+    r.first_row = first_row;
+    r.rows = rows;
+    r.row_stride = stride;
+    r.hop = h->hop;
+    r.gain = h->cfg.iq_gain;
+    return r;
+}
 
 // RO_PRECISION_F64: every size as radix-16 passes in double through HBM scratch, in chunks that fit it
 int launch_transform_f64(ro_stft *h, const void *d_iq, int format, int64_t first_row, int64_t rows, float *d_rows,
@@ -179,51 +209,29 @@ int launch_transform_f64(ro_stft *h, const void *d_iq, int format, int64_t first
             return launch_transform_f64_fused(h, d_iq, format, first_row, rows, d_rows, row_stride, s);
 #endif
     if (h->f64reg) {
-        ro::F64RegArgs r{};
-        r.iq = d_iq;
-        r.window_k = h->d_f64r_window;
-        r.tw0 = h->d_f64r_tw[0];
-        r.tw1 = h->d_f64r_tw[1];
-        r.tw2 = h->d_f64r_tw[2];
-        r.tw3 = h->d_f64r_tw[3];
-        r.rows_out = d_rows;
-        r.first_row = first_row;
-        r.rows = rows;
-        r.row_stride = row_stride;
-        r.hop = h->hop;
-        r.gain = h->cfg.iq_gain;
+        ro::F64RegArgs r = make_f64reg_args(h, d_iq, first_row, rows, d_rows, row_stride);
         r.stamps = h->d_stamps;
         HIP_TRY(ro::launch_f64reg(h->bins, format, r, s));
         return RO_OK;
     }
-    if (!h->d_scratch_d[0]) {
+    if (!h->scratch_rows_d) {
         int64_t mib = RO_F64_SCRATCH_MB;
 #ifdef RO_DIAG
         if (const char *e = getenv("RO_F64_SCRATCH_MB")) mib = std::max(1, atoi(e));     // tools/r4/strict_sweep.sh
 #endif
         h->scratch_rows_d = std::max<int64_t>(1, (mib << 20) / ((int64_t)h->bins * 16));
-        for (int i = 0; i < 2; ++i)
-            HIP_TRY(hipMalloc(&h->d_scratch_d[i], (size_t)h->scratch_rows_d * h->bins * sizeof(double2)));
     }
+    for (auto &blk : h->d_scratch_d)             // (each block on its own: a call after a failed one never launches without one)
+        if (!blk) HIP_TRY(blk.alloc((size_t)h->scratch_rows_d * h->bins));
     int radix[8];
     const int passes = ro::f64_radices(h->bins, radix);
     if (passes < 2) return fail(RO_ERR_UNSUPPORTED, "no FP64 pass plan for bins = %d", h->bins);
     for (int64_t done = 0; done < rows; done += h->scratch_rows_d) {
         const int64_t n = std::min(h->scratch_rows_d, rows - done);
-        ro::BigArgsD b{};
-        b.iq = d_iq;
-        b.window = h->d_window;
-        b.tw = h->d_tw_f64;
-        b.first_row = first_row + done;
-        b.rows = n;
-        b.row_stride = row_stride;
-        b.hop = h->hop;
-        b.n = h->bins;
-        b.gain = h->cfg.iq_gain;
+        ro::BigArgsD b = make_bigd_args(h, d_iq, first_row + done, n, d_rows + done * row_stride, row_stride);
         // two passes per kernel where the pair fits its LDS tile (radix 16 followed by any radix, bins >= 4096): half
         // the trips through the scratch blocks
         int ns = 1, hop_idx = 0;
-        b.rows_out = d_rows + done * row_stride;
         for (int p = 0; p < passes;) {
             const bool pair = h->bins >= 4096 && p + 1 < passes && radix[p] == 16;
             const int last_p = pair ? p + 1 : p;
@@ -319,8 +327,9 @@ int ensure_ln_part(ro_stft *h, int64_t rows)
     // sized generously the first time (16 bytes per row) and doubled after that, so that the device-wide wait a
     // regrow needs -- an earlier launch may still be writing the old block -- happens at most a few times per handle
     int64_t want = std::max<int64_t>(rows, std::max<int64_t>(65536, 2 * h->ln_part_rows));
-    if (h->d_ln_part) { (void)hipDeviceSynchronize(); (void)hipFree(h->d_ln_part); h->d_ln_part = nullptr; h->ln_part_rows = 0; }
-    HIP_TRY(hipMalloc(&h->d_ln_part, (size_t)want * 4 * sizeof(float)));
+    if (h->d_ln_part) (void)hipDeviceSynchronize();
+    h->ln_part_rows = 0;
+    HIP_TRY(h->d_ln_part.alloc((size_t)want * 4));
     h->ln_part_rows = want;
     return RO_OK;
 }
@@ -398,11 +407,9 @@ int launch_transform(ro_stft *h, const void *d_iq, int format, int64_t first_row
                     if (h->stream && h->stream != s) HIP_TRY(hipStreamSynchronize(h->stream));
                     for (ro_stft::Slot &sl : h->slot)
                         if (sl.gstream && sl.gstream != s) HIP_TRY(hipStreamSynchronize(sl.gstream));
-                    HIP_TRY(hipFree(h->d_four_z));
-                    h->d_four_z = nullptr;
-                    h->four_rows = 0;
                 }
-                HIP_TRY(hipMalloc(&h->d_four_z, (size_t)want * h->bins * 2 * sizeof(float)));
+                h->four_rows = 0;
+                HIP_TRY(h->d_four_z.alloc((size_t)want * h->bins * 2));
                 h->four_rows = want;
             }
         }
@@ -602,37 +609,31 @@ extern "C" int ro_stft_create(const ro_stft_config_t *cfg_in, ro_stft_t **out)
     CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     CREATE_TRY(hipEventCreate(&h->ev0));
     CREATE_TRY(hipEventCreate(&h->ev1));
-    CREATE_TRY(hipMalloc(&h->d_window, sizeof(float) * h->bins));
-    CREATE_TRY(hipMalloc(&h->d_ln_keys, 16 * 2 * sizeof(unsigned)));
-    CREATE_TRY(hipMalloc(&h->d_twiddles, sizeof(float2) * std::max<size_t>(tw.size(), 1)));
-    CREATE_TRY(hipMemcpy(h->d_window, h->window.data(), sizeof(float) * h->bins, hipMemcpyHostToDevice));
+    CREATE_TRY(h->d_window.upload(h->window));
+    CREATE_TRY(h->d_ln_keys.alloc(16 * 2));                      // (never memset: every call initialises the pair it uses)
+    if (tw.empty()) CREATE_TRY(h->d_twiddles.alloc(1));          // (a handle without stage tables still hands a pointer on)
+    else CREATE_TRY(h->d_twiddles.upload(tw));
     if (!h->big && !h->czt) {
         std::vector<float> wk((size_t)h->bins);
         if (!ro::stft_window_layout(h->bins, h->window.data(), wk.data())) {
             ro_stft_destroy(h);
             return fail(RO_ERR_UNSUPPORTED, "no window layout for bins=%d", h->bins);
         }
-        CREATE_TRY(hipMalloc(&h->d_window_k, sizeof(float) * h->bins));
-        CREATE_TRY(hipMemcpy(h->d_window_k, wk.data(), sizeof(float) * h->bins, hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_window_k.upload(wk));
         if (h->bins == 32768) {
             ro::stft32k_window_layout(h->window.data(), wk.data());
-            CREATE_TRY(hipMalloc(&h->d_window_k32, sizeof(float) * h->bins));
-            CREATE_TRY(hipMemcpy(h->d_window_k32, wk.data(), sizeof(float) * h->bins, hipMemcpyHostToDevice));
+            CREATE_TRY(h->d_window_k32.upload(wk));
         }
     }
-    if (!tw.empty())
-        CREATE_TRY(hipMemcpy(h->d_twiddles, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
     if (plan_bins) {
         const int units = ro::stft_packed_twiddle_count(plan_bins);
         std::vector<float4> pk((size_t)std::max(units, 1));
         if (units > 0) ro::stft_pack_twiddles(plan_bins, tw.data(), pk.data());
-        CREATE_TRY(hipMalloc(&h->d_twiddles_k, sizeof(float4) * pk.size()));
-        CREATE_TRY(hipMemcpy(h->d_twiddles_k, pk.data(), sizeof(float4) * pk.size(), hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_twiddles_k.upload(pk));
     }
     if (h->f64) {
         std::vector<double2> full = build_full_twiddles_f64(h->bins);
-        CREATE_TRY(hipMalloc(&h->d_tw_f64, sizeof(double2) * full.size()));
-        CREATE_TRY(hipMemcpy(h->d_tw_f64, full.data(), sizeof(double2) * full.size(), hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_tw_f64.upload(full));
         h->f64reg = ro::f64reg_supported(h->bins);
 #ifdef RO_DIAG
         if (const char *e = getenv("RO_F64_HBM")) h->f64reg = h->f64reg && atoi(e) == 0;   // the through-HBM passes, for A/B
@@ -640,14 +641,10 @@ extern "C" int ro_stft_create(const ro_stft_config_t *cfg_in, ro_stft_t **out)
         if (h->f64reg) {
             ro::F64RegTables t;
             ro::f64reg_tables(h->bins, h->window.data(), t);
-            CREATE_TRY(hipMalloc(&h->d_f64r_window, sizeof(float) * t.window_k.size()));
-            CREATE_TRY(hipMemcpy(h->d_f64r_window, t.window_k.data(), sizeof(float) * t.window_k.size(), hipMemcpyHostToDevice));
+            CREATE_TRY(h->d_f64r_window.upload(t.window_k));
             const std::vector<double2> *tabs[4] = {&t.tw0, &t.tw1, &t.tw2, &t.tw3};
-            for (int i = 0; i < 4; ++i) {
-                if (tabs[i]->empty()) continue;
-                CREATE_TRY(hipMalloc(&h->d_f64r_tw[i], sizeof(double2) * tabs[i]->size()));
-                CREATE_TRY(hipMemcpy(h->d_f64r_tw[i], tabs[i]->data(), sizeof(double2) * tabs[i]->size(), hipMemcpyHostToDevice));
-            }
+            for (int i = 0; i < 4; ++i)
+                if (!tabs[i]->empty()) CREATE_TRY(h->d_f64r_tw[i].upload(*tabs[i]));
         }
     }
     if (h->big && h->dec > 1) {
@@ -659,13 +656,11 @@ extern "C" int ro_stft_create(const ro_stft_config_t *cfg_in, ro_stft_t **out)
                 const long double ang = -two_pi * (long double)((long long)r * k) / (long double)h->bins;
                 tc[(size_t)r * h->sub_bins + k] = make_float2((float)cosl(ang), (float)sinl(ang));
             }
-        CREATE_TRY(hipMalloc(&h->d_tw_combine, sizeof(float2) * tc.size()));
-        CREATE_TRY(hipMemcpy(h->d_tw_combine, tc.data(), sizeof(float2) * tc.size(), hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_tw_combine.upload(tc));
     }
     if (h->big && h->dec > 1) {
         std::vector<float> ones((size_t)h->sub_bins, 1.0f);
-        CREATE_TRY(hipMalloc(&h->d_ones, sizeof(float) * ones.size()));
-        CREATE_TRY(hipMemcpy(h->d_ones, ones.data(), sizeof(float) * ones.size(), hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_ones.upload(ones));
     }
     if (h->dif) {
         std::vector<float> wk((size_t)h->bins);
@@ -675,8 +670,7 @@ extern "C" int ro_stft_create(const ro_stft_config_t *cfg_in, ro_stft_t **out)
                 ro_stft_destroy(h);
                 return fail(RO_ERR_UNSUPPORTED, "no window layout for bins=%d", h->sub_bins);
             }
-        CREATE_TRY(hipMalloc(&h->d_window_dif, sizeof(float) * wk.size()));
-        CREATE_TRY(hipMemcpy(h->d_window_dif, wk.data(), sizeof(float) * wk.size(), hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_window_dif.upload(wk));
         std::vector<float2> td((size_t)h->dec);
         const long double two_pi = 8.0L * atanl(1.0L);
         for (int j = 0; j < h->dec; ++j) {
@@ -686,8 +680,7 @@ extern "C" int ro_stft_create(const ro_stft_config_t *cfg_in, ro_stft_t **out)
             if ((4 * j) % h->dec == 0) { c = roundl(c); sn = roundl(sn); }
             td[(size_t)j] = make_float2((float)c, (float)sn);
         }
-        CREATE_TRY(hipMalloc(&h->d_dif_tw, sizeof(float2) * td.size()));
-        CREATE_TRY(hipMemcpy(h->d_dif_tw, td.data(), sizeof(float2) * td.size(), hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_dif_tw.upload(td));
         // residue q's rotation W_bins^(m q) as a shift of the bin index by q / dec: per stage (32, 32 x 32, 32^3 points
         // behind it) the powers 1, 2, 4, 8, 16 of exp(-2 pi i (q / dec) / M), each rounded once from long double
         std::vector<float2> ts((size_t)h->dec * 16, make_float2(1.0f, 0.0f));
@@ -698,21 +691,16 @@ extern "C" int ro_stft_create(const ro_stft_config_t *cfg_in, ro_stft_t **out)
                     const long double ang = -two_pi * ((long double)q / (long double)h->dec) * (long double)(1 << i) / span[st];
                     ts[(size_t)q * 16 + st * 5 + i] = make_float2((float)cosl(ang), (float)sinl(ang));
                 }
-        CREATE_TRY(hipMalloc(&h->d_dif_shift, sizeof(float2) * ts.size()));
-        CREATE_TRY(hipMemcpy(h->d_dif_shift, ts.data(), sizeof(float2) * ts.size(), hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_dif_shift.upload(ts));
     }
     if (h->four) {
         std::vector<float> wa;
         std::vector<float2> ta, tb, tr;
         ro::fourstep_tables(h->bins, h->window.data(), wa, ta, tb, tr);
-        CREATE_TRY(hipMalloc(&h->d_four_window, sizeof(float) * wa.size()));
-        CREATE_TRY(hipMemcpy(h->d_four_window, wa.data(), sizeof(float) * wa.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&h->d_four_tw_a, sizeof(float2) * ta.size()));
-        CREATE_TRY(hipMemcpy(h->d_four_tw_a, ta.data(), sizeof(float2) * ta.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&h->d_four_tw_b, sizeof(float2) * tb.size()));
-        CREATE_TRY(hipMemcpy(h->d_four_tw_b, tb.data(), sizeof(float2) * tb.size(), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&h->d_four_tw_r, sizeof(float2) * tr.size()));
-        CREATE_TRY(hipMemcpy(h->d_four_tw_r, tr.data(), sizeof(float2) * tr.size(), hipMemcpyHostToDevice));
+        CREATE_TRY(h->d_four_window.upload(wa));
+        CREATE_TRY(h->d_four_tw_a.upload(ta));
+        CREATE_TRY(h->d_four_tw_b.upload(tb));
+        CREATE_TRY(h->d_four_tw_r.upload(tr));
     }
     if (h->czt) {
         const int rc = czt_setup(h);
@@ -745,58 +733,16 @@ extern "C" int ro_stft_destroy(ro_stft_t *h)
     for (ro_stft::Slot &sl : h->slot)                       // graphed batches and their downloads run on the slots' own streams
         if (sl.gstream) (void)hipStreamSynchronize(sl.gstream);
     free_stream_slots(h);
-    if (h->d_window) (void)hipFree(h->d_window);
-    if (h->d_window_k) (void)hipFree(h->d_window_k);
-    if (h->d_window_k32) (void)hipFree(h->d_window_k32);
-    if (h->d_ln_keys) (void)hipFree(h->d_ln_keys);
-    if (h->d_twiddles) (void)hipFree(h->d_twiddles);
-    if (h->d_twiddles_k) (void)hipFree(h->d_twiddles_k);
-    if (h->d_stamps) (void)hipFree(h->d_stamps);
     while (!h->ready.empty()) {
         destroy_batch(h->ready.front());
         h->ready.pop_front();
     }
     for (Batch *b : h->batch_pool) destroy_batch(b);
-    if (h->d_tw_combine) (void)hipFree(h->d_tw_combine);
-    if (h->d_spec) (void)hipFree(h->d_spec);
-    if (h->d_window_dif) (void)hipFree(h->d_window_dif);
     if (h->inner) (void)ro_stft_destroy(h->inner);
-    if (h->d_cw) (void)hipFree(h->d_cw);
-    if (h->d_bc) (void)hipFree(h->d_bc);
-    if (h->d_czt_a) (void)hipFree(h->d_czt_a);
-    if (h->d_czt_A) (void)hipFree(h->d_czt_A);
-    if (h->d_czt_mag) (void)hipFree(h->d_czt_mag);
-    if (h->d_spec2) (void)hipFree(h->d_spec2);
-    if (h->d_four_window) (void)hipFree(h->d_four_window);
-    if (h->d_four_tw_a) (void)hipFree(h->d_four_tw_a);
-    if (h->d_four_tw_b) (void)hipFree(h->d_four_tw_b);
-    if (h->d_four_tw_r) (void)hipFree(h->d_four_tw_r);
-    if (h->d_four_z) (void)hipFree(h->d_four_z);
-    if (h->d_ones) (void)hipFree(h->d_ones);
-    if (h->d_dif_tw) (void)hipFree(h->d_dif_tw);
-    if (h->d_dif_shift) (void)hipFree(h->d_dif_shift);
-    if (h->d_tw_f64) (void)hipFree(h->d_tw_f64);
-    if (h->d_f64r_window) (void)hipFree(h->d_f64r_window);
-    for (int i = 0; i < 4; ++i)
-        if (h->d_f64r_tw[i]) (void)hipFree(h->d_f64r_tw[i]);
-    if (h->d_ln_part) (void)hipFree(h->d_ln_part);
-    if (h->d_band_tw) (void)hipFree(h->d_band_tw);
-    if (h->d_band_t1) (void)hipFree(h->d_band_t1);
-    if (h->d_band_t2) (void)hipFree(h->d_band_t2);
-    if (h->d_band_part) (void)hipFree(h->d_band_part);
-    if (h->d_band64_tw) (void)hipFree(h->d_band64_tw);
-    if (h->d_band64_t1) (void)hipFree(h->d_band64_t1);
-    if (h->d_band64_t2) (void)hipFree(h->d_band64_t2);
-    if (h->d_band64_part) (void)hipFree(h->d_band64_part);
-    for (int i = 0; i < 2; ++i)
-        if (h->d_scratch_d[i]) (void)hipFree(h->d_scratch_d[i]);
-    if (h->d_f64_ring) (void)hipFree(h->d_f64_ring);
-    if (h->d_f64_ctl) (void)hipFree(h->d_f64_ctl);
-    if (h->h_f64_err) (void)hipHostFree(h->h_f64_err);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                       // ... and with it every device and pinned block (ro_owned.h)
     return RO_OK;
 }
 
@@ -809,7 +755,7 @@ extern "C" int ro_stft_debug_stamps(ro_stft_t *h, unsigned long long *out, int m
     const int words = 4096 * 16;
     if (!h->d_stamps) {
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipMalloc(&h->d_stamps, sizeof(unsigned long long) * words));
+        HIP_TRY(h->d_stamps.alloc(words));
         HIP_TRY(hipMemset(h->d_stamps, 0, sizeof(unsigned long long) * words));
         return RO_OK;
     }
@@ -852,10 +798,11 @@ extern "C" int ro_stft_set_bands(ro_stft_t *h, const ro_bands_t *bands)
 // ---------------------------------------------------------------------------
 // resident path
 // ---------------------------------------------------------------------------
-// ro_stft_run_resident and ro_stft_run_resident_sets: the same launches, plus scan_sets_kernel when d_extra is given
+// ro_stft_run_resident, ro_stft_run_resident_sets and ro_stft_run_resident_ln: the same launches, plus scan_sets_kernel
+// when d_extra is given, plus the tile's log and its range when d_ln / d_minmax are
 static int run_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row, int64_t rows,
                         float *d_rows, int64_t row_stride, float *d_tile, ro_scan_record_t *d_records,
-                        ro_scan_record_t *d_extra, void *stream)
+                        ro_scan_record_t *d_extra, void *stream, float *d_ln = nullptr, float *d_minmax = nullptr)
 {
     int rc = validate_resident(h, d_iq, format, samples, first_row, rows, d_rows, row_stride, d_tile,
                                d_records);
@@ -865,9 +812,10 @@ static int run_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samp
     if (rows == 0) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;      // NULL = the default (null) stream, like any HIP launch
-    rc = launch_transform(h, d_iq, format, first_row, rows, d_rows, row_stride, s, d_tile, d_records);
+    // (the fused epilogue always writes the log when asked for its range: the partial min / max come with it)
+    rc = launch_transform(h, d_iq, format, first_row, rows, d_rows, row_stride, s, d_tile, d_records, d_ln);
     if (rc != RO_OK) return rc;
-    rc = launch_tile_and_scan(h, d_rows, row_stride, rows, d_tile, d_records, s, nullptr, nullptr, d_extra);
+    rc = launch_tile_and_scan(h, d_rows, row_stride, rows, d_tile, d_records, s, d_ln, d_minmax, d_extra);
     if (rc != RO_OK) return rc;
     h->stat_launches += 1;
     h->stat_rows += rows;
@@ -897,17 +845,9 @@ extern "C" int ro_stft_run_resident_ln(ro_stft_t *h, const void *d_iq, int forma
     if (!h->cfg.tile_ln) return fail(RO_ERR_STATE, "this handle was not created with tile_ln");
     if (!d_tile) return fail(RO_ERR_INVALID, "the log image is cut from the tile: d_tile is required");
     if (d_ln_minmax && !d_ln_tile) return fail(RO_ERR_INVALID, "the range comes with the log image: pass d_ln_tile too");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    // the fused epilogue always writes the log when asked for its range (the partial min / max come with it)
-    float *ln = d_ln_tile;
-    rc = launch_transform(h, d_iq, format, first_row, rows, d_rows, row_stride, s, d_tile, d_records, ln);
-    if (rc != RO_OK) return rc;
-    rc = launch_tile_and_scan(h, d_rows, row_stride, rows, d_tile, d_records, s, ln, d_ln_minmax);
-    if (rc != RO_OK) return rc;
-    h->stat_launches += 1;
-    h->stat_rows += rows;
-    return RO_OK;
+    // (run_resident repeats validate_resident, which passes again, and sets the device)
+    return run_resident(h, d_iq, format, samples, first_row, rows, d_rows, row_stride, d_tile, d_records, nullptr, stream,
+                        d_ln_tile, d_ln_minmax);
 }
 
 extern "C" int ro_stft_spectra_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples,
@@ -924,19 +864,7 @@ extern "C" int ro_stft_spectra_resident(ro_stft_t *h, const void *d_iq, int form
         // kernel's sizes only
         if (!h->f64reg)
             return fail(RO_ERR_UNSUPPORTED, "complex spectra of RO_PRECISION_F64 handles are available up to 65536 bins");
-        ro::F64RegArgs r{};
-        r.iq = d_iq;
-        r.window_k = h->d_f64r_window;
-        r.tw0 = h->d_f64r_tw[0];
-        r.tw1 = h->d_f64r_tw[1];
-        r.tw2 = h->d_f64r_tw[2];
-        r.tw3 = h->d_f64r_tw[3];
-        r.rows_out = d_spectra;
-        r.first_row = first_row;
-        r.rows = rows;
-        r.row_stride = stride;
-        r.hop = h->hop;
-        r.gain = h->cfg.iq_gain;
+        ro::F64RegArgs r = make_f64reg_args(h, d_iq, first_row, rows, d_spectra, stride);
         r.spectra = 1;
         HIP_TRY(ro::launch_f64reg(h->bins, format, r, (hipStream_t)stream));
         return RO_OK;
@@ -1053,79 +981,86 @@ extern "C" int ro_bands_hull(const ro_bands_t *b, int bins, int tile_first_col, 
 
 namespace {
 
-// exp(-2 pi i e / n) for an exactly reduced integer phase e in [0, n), evaluated in double and narrowed once
-float2 unit_root(int64_t e, int64_t n)
+// exp(-2 pi i e / n) for an exactly reduced integer phase e in [0, n): the float tables' evaluated in double and narrowed
+// once, the double tables' evaluated in long double and rounded once
+void unit_root(int64_t e, int64_t n, float2 &out)
 {
     const double ang = -2.0 * M_PI * (double)e / (double)n;
-    return make_float2((float)cos(ang), (float)sin(ang));
+    out = make_float2((float)cos(ang), (float)sin(ang));
+}
+void unit_root(int64_t e, int64_t n, double2 &out)
+{
+    const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)e / (long double)n;
+    out = make_double2((double)cosl(ang), (double)sinl(ang));
 }
 
 // the tables of band [first_col, +cols), uploaded on first use and kept until another band is asked for
-int ensure_band_tables(ro_stft *h, const ro::BandPlan &p, int first_col, int cols)
+template <typename T, typename Plan>
+int ensure_band_tables(ro_stft *h, BandState<T> &st, const Plan &p, int first_col, int cols)
 {
     if (h->band_first == first_col && h->band_cols == cols) return RO_OK;
-    if (h->d_band_t1) {                                 // an earlier launch may still be reading the old tables
-        HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(h->d_band_tw); h->d_band_tw = nullptr;
-        (void)hipFree(h->d_band_t1); h->d_band_t1 = nullptr;
-        (void)hipFree(h->d_band_t2); h->d_band_t2 = nullptr;
-        h->band_first = -1;
-        h->band_cols = 0;
-    }
+    if (st.tw || st.t1 || st.t2) HIP_TRY(hipDeviceSynchronize());     // an earlier launch may still be reading the old tables
+    st.tw.reset();                                      // (all three, whichever a failed call before this one left behind)
+    st.t1.reset();
+    st.t2.reset();
+    h->band_first = -1;
+    h->band_cols = 0;
     const int64_t n = h->bins;
-    std::vector<float2> tw((size_t)p.m), t1((size_t)cols * p.a), t2((size_t)p.slabs * cols);
-    for (int j = 0; j < p.m; ++j) tw[(size_t)j] = unit_root(j, p.m);
+    std::vector<T> tw((size_t)p.m), t1((size_t)cols * p.a), t2((size_t)p.slabs * cols);
+    for (int j = 0; j < p.m; ++j) unit_root(j, p.m, tw[(size_t)j]);
     for (int j = 0; j < cols; ++j) {
         const int64_t k = ((int64_t)first_col + j + n / 2) % n;
-        for (int t = 0; t < p.a; ++t) t1[(size_t)j * p.a + t] = unit_root((t * k) % n, n);
-        for (int s = 0; s < p.slabs; ++s) t2[(size_t)s * cols + j] = unit_root(((int64_t)s * p.a * k) % n, n);
+        for (int t = 0; t < p.a; ++t) unit_root((t * k) % n, n, t1[(size_t)j * p.a + t]);
+        for (int s = 0; s < p.slabs; ++s) unit_root(((int64_t)s * p.a * k) % n, n, t2[(size_t)s * cols + j]);
     }
-    HIP_TRY(hipMalloc(&h->d_band_tw, sizeof(float2) * tw.size()));
-    HIP_TRY(hipMalloc(&h->d_band_t1, sizeof(float2) * t1.size()));
-    HIP_TRY(hipMalloc(&h->d_band_t2, sizeof(float2) * t2.size()));
-    HIP_TRY(hipMemcpy(h->d_band_tw, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_band_t1, t1.data(), sizeof(float2) * t1.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_band_t2, t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice));
+    HIP_TRY(st.tw.upload(tw));
+    HIP_TRY(st.t1.upload(t1));
+    HIP_TRY(st.t2.upload(t2));
     h->band_first = first_col;
     h->band_cols = cols;
     return RO_OK;
 }
 
-// exp(-2 pi i e / n) for an exactly reduced integer phase e in [0, n), evaluated in long double and rounded once
-double2 unit_root_d(int64_t e, int64_t n)
+// rows [first_row, +rows) of band [first_col, +cols) in one precision (Args = ro::BandArgs with launch_band, ro::Band64Args
+// with launch_band64): the tables, the partial sums, the launches chunk by chunk, the scan of the band image, the counters
+template <typename Args, typename T, typename Plan, typename Launch>
+int run_band(ro_stft *h, BandState<T> &st, const Plan &p, Launch launch, const void *d_iq, int format, int64_t first_row,
+             int64_t rows, int first_col, int cols, float *d_band, int64_t band_stride, const ro::ScanArgs *sc, hipStream_t s)
 {
-    const long double ang = -2.0L * 3.14159265358979323846264338327950288L * (long double)e / (long double)n;
-    return make_double2((double)cosl(ang), (double)sinl(ang));
-}
-
-// ... the same tables in double, for the FP64 band kernels (ro_band_f64.hip)
-int ensure_band64_tables(ro_stft *h, const ro::Band64Plan &p, int first_col, int cols)
-{
-    if (h->band_first == first_col && h->band_cols == cols) return RO_OK;
-    if (h->d_band64_t1) {                               // an earlier launch may still be reading the old tables
-        HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(h->d_band64_tw); h->d_band64_tw = nullptr;
-        (void)hipFree(h->d_band64_t1); h->d_band64_t1 = nullptr;
-        (void)hipFree(h->d_band64_t2); h->d_band64_t2 = nullptr;
-        h->band_first = -1;
-        h->band_cols = 0;
+    int rc = ensure_band_tables(h, st, p, first_col, cols);
+    if (rc != RO_OK) return rc;
+    // the partial sums: rows per chunk like the large transforms' scratch, 256 MiB at the most, one grid of <= 65535 rows
+    const size_t row_bytes = (size_t)p.slabs * cols * sizeof(T);
+    const int64_t chunk = std::min<int64_t>(std::min<int64_t>(rows, 65535),
+                                            std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / row_bytes)));
+    if ((size_t)chunk * row_bytes > st.part_bytes) {
+        if (st.part) HIP_TRY(hipDeviceSynchronize());   // (an earlier launch may still be using the old block)
+        st.part_bytes = 0;
+        HIP_TRY(st.part.alloc((size_t)chunk * row_bytes / sizeof(T)));
+        st.part_bytes = (size_t)chunk * row_bytes;
     }
-    const int64_t n = h->bins;
-    std::vector<double2> tw((size_t)p.m), t1((size_t)cols * p.a), t2((size_t)p.slabs * cols);
-    for (int j = 0; j < p.m; ++j) tw[(size_t)j] = unit_root_d(j, p.m);
-    for (int j = 0; j < cols; ++j) {
-        const int64_t k = ((int64_t)first_col + j + n / 2) % n;
-        for (int t = 0; t < p.a; ++t) t1[(size_t)j * p.a + t] = unit_root_d((t * k) % n, n);
-        for (int s = 0; s < p.slabs; ++s) t2[(size_t)s * cols + j] = unit_root_d(((int64_t)s * p.a * k) % n, n);
+    for (int64_t done = 0; done < rows; done += chunk) {
+        Args b{};
+        b.iq = d_iq;
+        b.window = h->d_window;
+        b.tw = st.tw;
+        b.t1 = st.t1;
+        b.t2 = st.t2;
+        b.part = st.part;
+        b.band_out = d_band + done * band_stride;
+        b.first_row = first_row + done;
+        b.rows = std::min(chunk, rows - done);
+        b.band_stride = band_stride;
+        b.hop = h->hop;
+        b.bins = h->bins;
+        b.first_col = first_col;
+        b.cols = cols;
+        b.gain = (decltype(b.gain))h->cfg.iq_gain;
+        HIP_TRY(launch(p, format, b, s));
     }
-    HIP_TRY(hipMalloc(&h->d_band64_tw, sizeof(double2) * tw.size()));
-    HIP_TRY(hipMalloc(&h->d_band64_t1, sizeof(double2) * t1.size()));
-    HIP_TRY(hipMalloc(&h->d_band64_t2, sizeof(double2) * t2.size()));
-    HIP_TRY(hipMemcpy(h->d_band64_tw, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_band64_t1, t1.data(), sizeof(double2) * t1.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_band64_t2, t2.data(), sizeof(double2) * t2.size(), hipMemcpyHostToDevice));
-    h->band_first = first_col;
-    h->band_cols = cols;
+    if (sc) HIP_TRY(ro::launch_scan(*sc, s));
+    h->stat_launches += 1;
+    h->stat_rows += rows;
     return RO_OK;
 }
 
@@ -1180,86 +1115,12 @@ extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format,
     if (rows > (int64_t)0x0fffffff) return fail(RO_ERR_INVALID, "too many rows in one launch");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    if (h->f64) {
-        int rc = ensure_band64_tables(h, p64, first_col, cols);
-        if (rc != RO_OK) return rc;
-        // the partial sums, chunked by rows exactly like the float32 ones below
-        const size_t row_bytes = (size_t)p64.slabs * cols * sizeof(double2);
-        const int64_t chunk = std::min<int64_t>(std::min<int64_t>(rows, 65535),
-                                                std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / row_bytes)));
-        if ((size_t)chunk * row_bytes > h->band64_part_bytes) {
-            if (h->d_band64_part) {                     // (an earlier launch may still be using the old block)
-                HIP_TRY(hipDeviceSynchronize());
-                HIP_TRY(hipFree(h->d_band64_part));
-                h->d_band64_part = nullptr;
-                h->band64_part_bytes = 0;
-            }
-            HIP_TRY(hipMalloc(&h->d_band64_part, (size_t)chunk * row_bytes));
-            h->band64_part_bytes = (size_t)chunk * row_bytes;
-        }
-        for (int64_t done = 0; done < rows; done += chunk) {
-            ro::Band64Args b{};
-            b.iq = d_iq;
-            b.window = h->d_window;
-            b.tw = h->d_band64_tw;
-            b.t1 = h->d_band64_t1;
-            b.t2 = h->d_band64_t2;
-            b.part = h->d_band64_part;
-            b.band_out = d_band + done * band_stride;
-            b.first_row = first_row + done;
-            b.rows = std::min(chunk, rows - done);
-            b.band_stride = band_stride;
-            b.hop = h->hop;
-            b.bins = h->bins;
-            b.first_col = first_col;
-            b.cols = cols;
-            b.gain = (double)h->cfg.iq_gain;
-            HIP_TRY(ro::launch_band64(p64, format, b, s));
-        }
-        if (d_records) HIP_TRY(ro::launch_scan(sc, s));
-        h->stat_launches += 1;
-        h->stat_rows += rows;
-        return RO_OK;
-    }
-    int rc = ensure_band_tables(h, p, first_col, cols);
-    if (rc != RO_OK) return rc;
-    // the partial sums: rows per chunk like the large transforms' scratch, 256 MiB at the most, one grid of <= 65535 rows
-    const size_t row_bytes = (size_t)p.slabs * cols * sizeof(float2);
-    const int64_t chunk = std::min<int64_t>(std::min<int64_t>(rows, 65535),
-                                            std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / row_bytes)));
-    if ((size_t)chunk * row_bytes > h->band_part_bytes) {
-        if (h->d_band_part) {                           // (an earlier launch may still be using the old block)
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipFree(h->d_band_part));
-            h->d_band_part = nullptr;
-            h->band_part_bytes = 0;
-        }
-        HIP_TRY(hipMalloc(&h->d_band_part, (size_t)chunk * row_bytes));
-        h->band_part_bytes = (size_t)chunk * row_bytes;
-    }
-    for (int64_t done = 0; done < rows; done += chunk) {
-        ro::BandArgs b{};
-        b.iq = d_iq;
-        b.window = h->d_window;
-        b.tw = h->d_band_tw;
-        b.t1 = h->d_band_t1;
-        b.t2 = h->d_band_t2;
-        b.part = h->d_band_part;
-        b.band_out = d_band + done * band_stride;
-        b.first_row = first_row + done;
-        b.rows = std::min(chunk, rows - done);
-        b.band_stride = band_stride;
-        b.hop = h->hop;
-        b.bins = h->bins;
-        b.first_col = first_col;
-        b.cols = cols;
-        b.gain = (float)h->cfg.iq_gain;
-        HIP_TRY(ro::launch_band(p, format, b, s));
-    }
-    if (d_records) HIP_TRY(ro::launch_scan(sc, s));
-    h->stat_launches += 1;
-    h->stat_rows += rows;
-    return RO_OK;
+    const ro::ScanArgs *scan = d_records ? &sc : nullptr;
+    if (h->f64)
+        return run_band<ro::Band64Args>(h, h->band64, p64, ro::launch_band64, d_iq, format, first_row, rows, first_col, cols,
+                                        d_band, band_stride, scan, s);
+    return run_band<ro::BandArgs>(h, h->band, p, ro::launch_band, d_iq, format, first_row, rows, first_col, cols, d_band,
+                                  band_stride, scan, s);
 }
 
 extern "C" int ro_stft_time_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples,

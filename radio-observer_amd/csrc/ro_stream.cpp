@@ -18,30 +18,14 @@ Batch *acquire_batch(ro_stft *h)
     Batch *b = new (std::nothrow) Batch();
     if (!b) return nullptr;
     b->capacity_rows = h->batch_rows;
-    if ((!h->sink &&
-         hipHostMalloc(reinterpret_cast<void **>(&b->data), (size_t)b->capacity_rows * h->out_cols * sizeof(float),
-                       hipHostMallocDefault) != hipSuccess) ||
-        hipHostMalloc(reinterpret_cast<void **>(&b->records), (size_t)b->capacity_rows * sizeof(ro_scan_record_t),
-                      hipHostMallocDefault) != hipSuccess ||
-        (h->extra_count > 0 &&
-         hipHostMalloc(reinterpret_cast<void **>(&b->extra),
-                       (size_t)b->capacity_rows * h->extra_count * sizeof(ro_scan_record_t), hipHostMallocDefault) != hipSuccess) ||
-        (h->cfg.tile_ln &&
-         (hipHostMalloc(reinterpret_cast<void **>(&b->ln), (size_t)b->capacity_rows * h->out_cols * sizeof(float),
-                        hipHostMallocDefault) != hipSuccess ||
-          hipHostMalloc(reinterpret_cast<void **>(&b->minmax), (size_t)b->capacity_rows * 2 * sizeof(float),
-                        hipHostMallocDefault) != hipSuccess)) ||
+    const size_t cap = (size_t)b->capacity_rows;
+    if ((!h->sink && b->data.alloc(cap * h->out_cols) != hipSuccess) ||
+        b->records.alloc(cap) != hipSuccess ||
+        (h->extra_count > 0 && b->extra.alloc(cap * h->extra_count) != hipSuccess) ||
+        (h->cfg.tile_ln && (b->ln.alloc(cap * h->out_cols) != hipSuccess || b->minmax.alloc(cap * 2) != hipSuccess)) ||
         hipEventCreateWithFlags(&b->done, hipEventDisableTiming) != hipSuccess ||
         hipEventCreate(&b->k0) != hipSuccess || hipEventCreate(&b->k1) != hipSuccess) {
-        if (b->data) (void)hipHostFree(b->data);
-        if (b->ln) (void)hipHostFree(b->ln);
-        if (b->minmax) (void)hipHostFree(b->minmax);
-        if (b->records) (void)hipHostFree(b->records);
-        if (b->extra) (void)hipHostFree(b->extra);
-        if (b->done) (void)hipEventDestroy(b->done);
-        if (b->k0) (void)hipEventDestroy(b->k0);
-        if (b->k1) (void)hipEventDestroy(b->k1);
-        delete b;
+        destroy_batch(b);
         return nullptr;
     }
     return b;
@@ -74,20 +58,19 @@ int ensure_stream_slots(ro_stft *h)
     // for its whole upload -> kernel -> download chain, ~90 us; with three streams a second batch in flight overlaps it.)
     ok(hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking)) && ok(hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
     for (auto &sl : h->slot) {
-        ok(hipMalloc(&sl.d_iq, in_samples * slot_sample_bytes(h))) &&
-            ok(hipMalloc(&sl.d_rows, (size_t)h->batch_rows * h->bins * sizeof(float))) &&
-            ok(hipMalloc(&sl.d_records, (size_t)h->batch_rows * sizeof(ro_scan_record_t))) &&
-            ok(hipHostMalloc(&sl.h_in, in_samples * slot_sample_bytes(h), hipHostMallocDefault)) &&
+        ok(sl.d_iq.alloc(in_samples * slot_sample_bytes(h))) &&
+            ok(sl.d_rows.alloc((size_t)h->batch_rows * h->bins)) &&
+            ok(sl.d_records.alloc((size_t)h->batch_rows)) &&
+            ok(sl.h_in.alloc(in_samples * slot_sample_bytes(h))) &&
             ok(hipEventCreateWithFlags(&sl.uploaded, hipEventDisableTiming)) &&
             ok(hipEventCreateWithFlags(&sl.computed, hipEventDisableTiming)) &&
             ok(hipEventCreateWithFlags(&sl.drained, hipEventDisableTiming));
         if (h->cfg.tile_cols > 0)
-            ok(hipMalloc(&sl.d_tile, (size_t)h->batch_rows * h->cfg.tile_cols * sizeof(float)));
+            ok(sl.d_tile.alloc((size_t)h->batch_rows * h->cfg.tile_cols));
         if (h->extra_count > 0)
-            ok(hipMalloc(&sl.d_extra, (size_t)h->batch_rows * h->extra_count * sizeof(ro_scan_record_t)));
+            ok(sl.d_extra.alloc((size_t)h->batch_rows * h->extra_count));
         if (h->cfg.tile_ln)
-            ok(hipMalloc(&sl.d_ln, (size_t)h->batch_rows * h->cfg.tile_cols * sizeof(float))) &&
-                ok(hipMalloc(&sl.d_minmax, (size_t)h->batch_rows * 2 * sizeof(float)));
+            ok(sl.d_ln.alloc((size_t)h->batch_rows * h->cfg.tile_cols)) && ok(sl.d_minmax.alloc((size_t)h->batch_rows * 2));
     }
     if (e != hipSuccess) {
         free_stream_slots(h);
@@ -348,34 +331,21 @@ namespace host {
 
 void destroy_batch(Batch *b)
 {
-    if (b->data) (void)hipHostFree(b->data);
-    if (b->ln) (void)hipHostFree(b->ln);
-    if (b->minmax) (void)hipHostFree(b->minmax);
-    if (b->records) (void)hipHostFree(b->records);
-    if (b->extra) (void)hipHostFree(b->extra);
     if (b->done) (void)hipEventDestroy(b->done);
     if (b->k0) (void)hipEventDestroy(b->k0);
     if (b->k1) (void)hipEventDestroy(b->k1);
-    delete b;
+    delete b;                                           // ... and with it its pinned blocks
 }
 
 void free_stream_slots(ro_stft *h)
 {
     for (auto &sl : h->slot) {
-        if (sl.d_iq) (void)hipFree(sl.d_iq);
-        if (sl.d_rows) (void)hipFree(sl.d_rows);
-        if (sl.d_tile) (void)hipFree(sl.d_tile);
-        if (sl.d_ln) (void)hipFree(sl.d_ln);
-        if (sl.d_minmax) (void)hipFree(sl.d_minmax);
-        if (sl.d_records) (void)hipFree(sl.d_records);
-        if (sl.d_extra) (void)hipFree(sl.d_extra);
-        if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.uploaded) (void)hipEventDestroy(sl.uploaded);
         if (sl.computed) (void)hipEventDestroy(sl.computed);
         if (sl.drained) (void)hipEventDestroy(sl.drained);
         if (sl.gexec) (void)hipGraphExecDestroy(sl.gexec);
         if (sl.gstream) (void)hipStreamDestroy(sl.gstream);
-        sl = ro_stft::Slot();
+        sl = ro_stft::Slot();                           // (frees the slot's device and pinned blocks)
     }
     if (h->s_in) (void)hipStreamDestroy(h->s_in);
     if (h->s_out) (void)hipStreamDestroy(h->s_out);
@@ -613,13 +583,13 @@ extern "C" int ro_stft_set_extra_bands(ro_stft_t *h, const ro_bands_t *sets, int
     for (auto &sl : h->slot) {
         if (sl.gstream) HIP_TRY(hipStreamSynchronize(sl.gstream));
         if (sl.gexec) { (void)hipGraphExecDestroy(sl.gexec); sl.gexec = nullptr; }
-        if (sl.d_extra) { (void)hipFree(sl.d_extra); sl.d_extra = nullptr; }
+        sl.d_extra.reset();
     }
     while (!h->batch_pool.empty()) { destroy_batch(h->batch_pool.back()); h->batch_pool.pop_back(); }
     h->extra_count = 0;
     if (h->slots_ready && count > 0)          // (else the first push allocates them with the other streaming buffers)
         for (auto &sl : h->slot)
-            HIP_TRY(hipMalloc(&sl.d_extra, (size_t)h->batch_rows * count * sizeof(ro_scan_record_t)));
+            HIP_TRY(sl.d_extra.alloc((size_t)h->batch_rows * count));
     for (int i = 0; i < count; ++i) h->extra[i] = sets[i];
     h->extra_count = count;
     return RO_OK;
