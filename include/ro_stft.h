@@ -325,8 +325,8 @@ int ro_stft_band_supported_precision(int bins, int cols, int precision);
  * src/BolidRecorder.cpp:313-317), the detect band (peak(), :323-335) widened by what average() reads around any peak
  * (:126-132, :338-347: [low_detect - avg_bins/2, low_detect + detect_width - 1 - avg_bins/2 + avg_bins)), and, if
  * tile_cols > 0, the tile (the snapshot's column cut, src/WaterfallBackend.cpp:176,204).
- * RO_ERR_INVALID if that range leaves [0, bins).  Pure host.  ONE band set: the band-only transform's records stay
- * single-set (the primary), and a hull over a handle's extra sets (ro_stft_set_extra_bands) is out of scope. */
+ * RO_ERR_INVALID if that range leaves [0, bins).  Pure host.  ONE band set and ONE range: ro_bands_windows below
+ * answers for several sets, and keeps apart what lies apart. */
 int ro_bands_hull(const ro_bands_t *bands, int bins, int tile_first_col, int tile_cols,
                   int *first_col, int *cols);
 
@@ -347,6 +347,54 @@ int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format, int64_t sa
                           int64_t first_row, int64_t rows, int first_col, int cols,
                           float *d_band, int64_t band_stride,
                           ro_scan_record_t *d_records, void *stream);
+
+/* ---- band-only transform over several column windows --------------------------
+ * What the recorders read of a row is seldom one run of columns: the noise band and the detect band of one detector lie
+ * apart (radio-observer.json: 409 and 436 columns whose hull, with the snapshot's 615, is 1365), and several detectors
+ * (ro_stft_set_extra_bands) watch different frequencies.  A WINDOW is one run of columns [first_col, first_col + cols)
+ * of the fft-shifted row; the calls below compute up to RO_MAX_BAND_WINDOWS of them in one pass, 1024 columns in all, and
+ * nothing of the columns between them.  (In X[k] = sum_a W^(a k) Z_a[k mod M] nothing asks the wanted k to be
+ * consecutive or their residues mod M to differ: two columns of one residue read the same value Z_a, each with its own
+ * twiddles.  A column's bits depend on its bin, on M and on the slab size only -- not on which other columns are asked
+ * for.)  Rate, float32, radio-observer.json's two windows at 32768 bins: 0.37 x the full rows with tile and records
+ * (profiles/band_windows.txt) -- the call serves shapes ro_stft_band_resident refuses and hosts that cannot afford the
+ * rows in HBM; it is not a faster way to the same records there. */
+#define RO_MAX_BAND_WINDOWS 8
+typedef struct ro_band_window {
+    int32_t first_col;             /* first column of the fft-shifted row           */
+    int32_t cols;                  /* >= 1                                          */
+} ro_band_window_t;
+
+/* 1 if the windows are valid and a kernel exists for them: 1 <= count <= RO_MAX_BAND_WINDOWS, every cols >= 1, every
+ * window inside [0, bins), ascending and not overlapping (touching is allowed), at most 1024 columns in all, and bins /
+ * precision as ro_stft_band_supported_precision asks for that total (the short transforms are the smallest of 256, 512,
+ * 1024 points that is at least the total).  Pure host. */
+int ro_stft_band_windows_supported(int bins, const ro_band_window_t *windows, int count, int precision);
+
+/* The windows that hold what `set_count` band sets (1 ... 8: a primary and its extras) read of a row, and the tile if
+ * tile_cols > 0.  Per set two intervals, the noise band and the detect band widened by the average's margin (the two
+ * ro_bands_hull joins into one); intervals that overlap or touch are merged; while more than RO_MAX_BAND_WINDOWS remain,
+ * the pair with the smallest gap is merged (the lower pair on a tie).  windows_out: RO_MAX_BAND_WINDOWS entries,
+ * ascending; *count_out of them are written.  RO_ERR_INVALID if an interval leaves [0, bins).  The total is not judged
+ * here: ask ro_stft_band_windows_supported.  Pure host. */
+int ro_bands_windows(const ro_bands_t *sets, int set_count, int bins, int tile_first_col, int tile_cols,
+                     ro_band_window_t *windows_out, int *count_out);
+
+/* ro_stft_band_resident over `count` windows.  Image layout: window w occupies floats [off_w, off_w + cols_w) of each
+ * band row, off_w the sum of the earlier windows' cols; band_stride >= the total, floats beyond the total in a row are
+ * not touched.  With count = 1 the bits are ro_stft_band_resident's.
+ * d_records (optional): the primary set's records.  d_extra (optional; RO_ERR_STATE without extra sets): the handle's
+ * extra sets' records, set s of row r at [r * extra_count + s] as in ro_stft_run_resident_sets.  Each requested set's
+ * noise band must lie inside one window and its detect band, average's margin included, inside one window (not
+ * necessarily the same) -- RO_ERR_INVALID naming the set and the columns otherwise.  The records are those of the scan
+ * kernels on the band image, the bands moved to image coordinates (- first_col_w + off_w); peak counts from low_detect.
+ * Precisions, formats, refusals, rows == 0 and the sample count: as ro_stft_band_resident.  Asynchronous on `stream`;
+ * uses handle scratch, so one launch of a handle in flight at a time. */
+int ro_stft_band_windows_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples,
+                                  int64_t first_row, int64_t rows,
+                                  const ro_band_window_t *windows, int count,
+                                  float *d_band, int64_t band_stride,
+                                  ro_scan_record_t *d_records, ro_scan_record_t *d_extra, void *stream);
 
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel

@@ -15,6 +15,7 @@ RO_WINDOW_NUTTALL, RO_WINDOW_HANN, RO_WINDOW_CUSTOM = 0, 1, 2
 RO_IQ_F32, RO_IQ_I16, RO_IQ_F64 = 0, 1, 2
 RO_PRECISION_F32, RO_PRECISION_F64 = 0, 1
 RO_MAX_EXTRA_BANDS = 7
+RO_MAX_BAND_WINDOWS = 8
 
 RO_OK = 0
 _ERR_NAMES = {-1: "RO_ERR_INVALID", -2: "RO_ERR_UNSUPPORTED", -3: "RO_ERR_HIP", -4: "RO_ERR_NOMEM",
@@ -31,6 +32,17 @@ class Bands(C.Structure):
     """ro_bands_t -- BolidRecorder::start's bin ranges (src/BolidRecorder.cpp:84-102)."""
     _fields_ = [("low_noise", C.c_int32), ("noise_width", C.c_int32), ("low_detect", C.c_int32),
                 ("detect_width", C.c_int32), ("avg_bins", C.c_int32)]
+
+
+class BandWindow(C.Structure):
+    """ro_band_window_t -- one run of columns [first_col, first_col + cols) of the fft-shifted row."""
+    _fields_ = [("first_col", C.c_int32), ("cols", C.c_int32)]
+
+    def __iter__(self):                                 # first_col, cols = window
+        return iter((self.first_col, self.cols))
+
+    def __repr__(self):
+        return "BandWindow(%d, %d)" % (self.first_col, self.cols)
 
 
 class ScanRecord(C.Structure):
@@ -121,6 +133,12 @@ _EXPORTS = {
     "ro_bands_hull": (C.c_int, [C.POINTER(Bands), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ro_stft_band_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                         C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ro_stft_band_windows_supported": (C.c_int, [C.c_int, C.POINTER(BandWindow), C.c_int, C.c_int]),
+    "ro_bands_windows": (C.c_int, [C.POINTER(Bands), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BandWindow),
+                                   C.POINTER(C.c_int)]),
+    "ro_stft_band_windows_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                                C.POINTER(BandWindow), C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -318,6 +336,29 @@ def bands_hull(bands, bins, tile_first_col=0, tile_cols=0):
     return first.value, cols.value
 
 
+def _windows(windows):
+    """a ctypes array of BandWindow from BandWindow objects or (first_col, cols) pairs"""
+    items = [w if isinstance(w, BandWindow) else BandWindow(*w) for w in windows]
+    return (BandWindow * max(len(items), 1))(*items), len(items)
+
+
+def band_windows_supported(bins, windows, precision=RO_PRECISION_F32):
+    """whether Stft.band_windows_resident can produce these windows (BandWindow or (first_col, cols) each) of a
+    `bins`-bin row on a handle of `precision` -- ro_stft_band_windows_supported"""
+    arr, n = _windows(windows)
+    return bool(library().ro_stft_band_windows_supported(bins, arr, n, precision))
+
+
+def bands_windows(sets, bins, tile_first_col=0, tile_cols=0):
+    """the windows (a list of BandWindow, ascending) that hold what the band sets `sets` (one Bands or a sequence of 1 ... 8)
+    and the tile read of a row, kept apart where they lie apart -- ro_bands_windows"""
+    sets = [sets] if isinstance(sets, Bands) else list(sets)
+    arr = (Bands * max(len(sets), 1))(*sets)
+    out, n = (BandWindow * RO_MAX_BAND_WINDOWS)(), C.c_int()
+    _check(library().ro_bands_windows(arr, len(sets), bins, tile_first_col, tile_cols, out, C.byref(n)))
+    return [BandWindow(out[i].first_col, out[i].cols) for i in range(n.value)]
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -481,6 +522,16 @@ class Stft:
         """columns [first_col, +cols) of the rows and nothing else (rows x band_stride float32), plus their scan records"""
         _check(library().ro_stft_band_resident(self._h, _ptr(d_iq), fmt, samples, first_row, rows, first_col, cols,
                                                _ptr(d_band), band_stride or cols, _ptr(d_records), _ptr(stream)))
+
+    def band_windows_resident(self, d_iq, fmt, samples, first_row, rows, windows, d_band, band_stride=None,
+                              d_records=None, d_extra=None, stream=None):
+        """the columns of `windows` (BandWindow or (first_col, cols) each, ascending) side by side in rows x band_stride
+        float32 and nothing else, plus the scan records of the primary (d_records) and the extra sets (d_extra)"""
+        arr, n = _windows(windows)
+        total = sum(arr[i].cols for i in range(n))
+        _check(library().ro_stft_band_windows_resident(self._h, _ptr(d_iq), fmt, samples, first_row, rows, arr, n,
+                                                       _ptr(d_band), band_stride or total, _ptr(d_records),
+                                                       _ptr(d_extra), _ptr(stream)))
 
     def scan_resident(self, d_rows, rows, d_records, row_stride=None, stream=None):
         _check(library().ro_stft_scan_resident(self._h, _ptr(d_rows), row_stride or self.bins, rows,

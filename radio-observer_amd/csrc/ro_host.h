@@ -30,6 +30,7 @@
 #include "ro_kernels.h"
 #include "ro_band.h"
 #include "ro_band_f64.h"
+#include "ro_band_windows.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -119,12 +120,13 @@ struct Batch {
 };
 
 // the band-only transform's device state in one precision (T = float2: ro_band.hip, double2: ro_band_f64.hip): the tables
-// of the last band asked for and the slabs' partial sums between the two kernels, grown on demand
+// of the last column windows asked for and the slabs' partial sums between the two kernels, grown on demand
 template <typename T>
 struct BandState {
     DeviceBlock<T> tw;                         // [m]: exp(-2 pi i j / m)
     DeviceBlock<T> t1;                         // [cols][a]: exp(-2 pi i t k / bins)
     DeviceBlock<T> t2;                         // [slabs][cols]: exp(-2 pi i (slab a) k / bins)
+    DeviceBlock<int32_t> kcell;                // [cols]: LDS cell of each image column's bin (ro_band_windows.h)
     DeviceBlock<T> part;                       // [rows of a chunk][slabs][cols]
     size_t part_bytes = 0;
 };
@@ -242,9 +244,10 @@ struct ro_stft {
     DeviceBlock<float> d_ln_part;
     int64_t ln_part_rows = 0;
 
-    // band-only transform (ro_stft_band_resident): band_first / band_cols say which band the tables belong to; a handle has
-    // one precision, so one of the two sets is in use (band64: RO_PRECISION_F64 handles of 131072 bins and above)
-    int     band_first = -1, band_cols = 0;
+    // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
+    // belong to (one window for the consecutive call; empty: none); a handle has one precision, so one of the two sets is
+    // in use (band64: RO_PRECISION_F64 handles of 131072 bins and above)
+    std::vector<ro_band_window_t> band_key;
     ro::host::BandState<float2>  band;
     ro::host::BandState<double2> band64;
 

@@ -994,40 +994,62 @@ void unit_root(int64_t e, int64_t n, double2 &out)
     out = make_double2((double)cosl(ang), (double)sinl(ang));
 }
 
-// the tables of band [first_col, +cols), uploaded on first use and kept until another band is asked for
+// the tables of the columns the windows list (image column j = the j-th column of the list, bin k(j)), uploaded on first
+// use and kept until another list is asked for
 template <typename T, typename Plan>
-int ensure_band_tables(ro_stft *h, BandState<T> &st, const Plan &p, int first_col, int cols)
+int ensure_band_tables(ro_stft *h, BandState<T> &st, const Plan &p, const ro_band_window_t *w, int count)
 {
-    if (h->band_first == first_col && h->band_cols == cols) return RO_OK;
-    if (st.tw || st.t1 || st.t2) HIP_TRY(hipDeviceSynchronize());     // an earlier launch may still be reading the old tables
-    st.tw.reset();                                      // (all three, whichever a failed call before this one left behind)
+    if ((int)h->band_key.size() == count &&
+        std::equal(w, w + count, h->band_key.begin(), [](const ro_band_window_t &x, const ro_band_window_t &y) {
+            return x.first_col == y.first_col && x.cols == y.cols;
+        }))
+        return RO_OK;
+    if (st.tw || st.t1 || st.t2 || st.kcell) HIP_TRY(hipDeviceSynchronize());     // an earlier launch may still be reading the old tables
+    st.tw.reset();                                      // (all four, whichever a failed call before this one left behind)
     st.t1.reset();
     st.t2.reset();
-    h->band_first = -1;
-    h->band_cols = 0;
+    st.kcell.reset();
+    h->band_key.clear();
     const int64_t n = h->bins;
+    std::vector<int64_t> ks;                            // the bins, in image order
+    for (int i = 0; i < count; ++i)
+        for (int c = 0; c < w[i].cols; ++c) ks.push_back(((int64_t)w[i].first_col + c + n / 2) % n);
+    const int cols = (int)ks.size();
     std::vector<T> tw((size_t)p.m), t1((size_t)cols * p.a), t2((size_t)p.slabs * cols);
+    std::vector<int32_t> kcell((size_t)cols);
     for (int j = 0; j < p.m; ++j) unit_root(j, p.m, tw[(size_t)j]);
     for (int j = 0; j < cols; ++j) {
-        const int64_t k = ((int64_t)first_col + j + n / 2) % n;
+        const int64_t k = ks[(size_t)j];
+        kcell[(size_t)j] = ro::band_cell(p.m, (int)(k % p.m)) * p.a;          // < a m: inside the workgroup's LDS image
+                                                                              // (read by the window-list kernels only)
         for (int t = 0; t < p.a; ++t) unit_root((t * k) % n, n, t1[(size_t)j * p.a + t]);
         for (int s = 0; s < p.slabs; ++s) unit_root(((int64_t)s * p.a * k) % n, n, t2[(size_t)s * cols + j]);
     }
     HIP_TRY(st.tw.upload(tw));
     HIP_TRY(st.t1.upload(t1));
     HIP_TRY(st.t2.upload(t2));
-    h->band_first = first_col;
-    h->band_cols = cols;
+    HIP_TRY(st.kcell.upload(kcell));
+    h->band_key.assign(w, w + count);
     return RO_OK;
 }
 
-// rows [first_row, +rows) of band [first_col, +cols) in one precision (Args = ro::BandArgs with launch_band, ro::Band64Args
-// with launch_band64): the tables, the partial sums, the launches chunk by chunk, the scan of the band image, the counters
+// how each kernel family is told which columns the image shows: the consecutive call's kernels (ro_band.hip,
+// ro_band_f64.hip) derive the bins from first_col, the window-list kernels read the table
+inline void set_columns(ro::BandArgs &b, const ro_band_window_t *w, const int32_t *) { b.first_col = w[0].first_col; }
+inline void set_columns(ro::Band64Args &b, const ro_band_window_t *w, const int32_t *) { b.first_col = w[0].first_col; }
+inline void set_columns(ro::BandWinArgs &b, const ro_band_window_t *, const int32_t *kcell) { b.kcell = kcell; }
+inline void set_columns(ro::Band64WinArgs &b, const ro_band_window_t *, const int32_t *kcell) { b.kcell = kcell; }
+
+// rows [first_row, +rows) of the `cols` columns the windows list, in one precision and one kernel family (Args =
+// ro::BandArgs with launch_band, ro::Band64Args with launch_band64: one window; ro::BandWinArgs with launch_band_windows,
+// ro::Band64WinArgs with launch_band64_windows: any list): the tables, the partial sums, the launches chunk by chunk, the
+// scans of the band image, the counters
 template <typename Args, typename T, typename Plan, typename Launch>
 int run_band(ro_stft *h, BandState<T> &st, const Plan &p, Launch launch, const void *d_iq, int format, int64_t first_row,
-             int64_t rows, int first_col, int cols, float *d_band, int64_t band_stride, const ro::ScanArgs *sc, hipStream_t s)
+             int64_t rows, const ro_band_window_t *w, int count, int cols, float *d_band, int64_t band_stride,
+             const ro::ScanArgs *sc, const ro::ScanSetsArgs *ss, hipStream_t s)
 {
-    int rc = ensure_band_tables(h, st, p, first_col, cols);
+    int rc = ensure_band_tables(h, st, p, w, count);
     if (rc != RO_OK) return rc;
     // the partial sums: rows per chunk like the large transforms' scratch, 256 MiB at the most, one grid of <= 65535 rows
     const size_t row_bytes = (size_t)p.slabs * cols * sizeof(T);
@@ -1046,6 +1068,7 @@ int run_band(ro_stft *h, BandState<T> &st, const Plan &p, Launch launch, const v
         b.tw = st.tw;
         b.t1 = st.t1;
         b.t2 = st.t2;
+        set_columns(b, w, st.kcell);
         b.part = st.part;
         b.band_out = d_band + done * band_stride;
         b.first_row = first_row + done;
@@ -1053,22 +1076,19 @@ int run_band(ro_stft *h, BandState<T> &st, const Plan &p, Launch launch, const v
         b.band_stride = band_stride;
         b.hop = h->hop;
         b.bins = h->bins;
-        b.first_col = first_col;
         b.cols = cols;
         b.gain = (decltype(b.gain))h->cfg.iq_gain;
         HIP_TRY(launch(p, format, b, s));
     }
     if (sc) HIP_TRY(ro::launch_scan(*sc, s));
+    if (ss) HIP_TRY(ro::launch_scan_sets(*ss, s));
     h->stat_launches += 1;
     h->stat_rows += rows;
     return RO_OK;
 }
 
-}  // namespace
-
-extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
-                                     int64_t rows, int first_col, int cols, float *d_band, int64_t band_stride,
-                                     ro_scan_record_t *d_records, void *stream)
+// what both band calls refuse about the handle and the sample format, before they look at the columns
+int check_band_handle(const ro_stft *h, int format)
 {
     if (!h) return fail(RO_ERR_INVALID, "null handle");
     if (h->czt) return fail(RO_ERR_UNSUPPORTED, "the band-only transform needs power-of-two bins (got %d)", h->bins);
@@ -1080,6 +1100,141 @@ extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format,
                                         "(RO_IQ_F64 on RO_PRECISION_F64 handles of 131072 bins and above)");
     if (format != RO_IQ_F32 && format != RO_IQ_I16 && format != RO_IQ_F64)
         return fail(RO_ERR_INVALID, "resident input must be RO_IQ_F32, RO_IQ_I16 or RO_IQ_F64 (got %d)", format);
+    return RO_OK;
+}
+
+// ... and what they refuse once the columns and the scans are settled; *go = false: rows == 0, RO_OK and nothing to do
+int check_band_input(const ro_stft *h, const void *d_iq, int64_t samples, int64_t first_row, int64_t rows,
+                     const float *d_band, bool *go)
+{
+    *go = false;
+    if (rows == 0) return RO_OK;
+    if (!d_iq) return fail(RO_ERR_INVALID, "null input pointer");
+    if (!d_band) return fail(RO_ERR_INVALID, "d_band is required");
+    const int64_t last = (first_row + rows - 1) * (int64_t)h->hop + h->bins;
+    if (last > samples)
+        return fail(RO_ERR_INVALID, "rows [%lld,+%lld) need %lld samples, buffer holds %lld", (long long)first_row,
+                    (long long)rows, (long long)last, (long long)samples);
+    if (rows > (int64_t)0x0fffffff) return fail(RO_ERR_INVALID, "too many rows in one launch");
+    *go = true;
+    return RO_OK;
+}
+
+// the two intervals a band set reads of a row: its noise band, and its detect band widened by what average() reads around
+// any peak (ro_bands_hull has the sources)
+struct SetReads { int64_t noise_lo, noise_hi, detect_lo, detect_hi; };
+SetReads set_reads(const ro_bands_t &b)
+{
+    return {b.low_noise, (int64_t)b.low_noise + b.noise_width, (int64_t)b.low_detect - b.avg_bins / 2,
+            (int64_t)b.low_detect + b.detect_width - 1 - b.avg_bins / 2 + b.avg_bins};
+}
+
+// the window that holds columns [lo, hi) whole, and where it starts in the image; -1: none
+int window_of(const ro_band_window_t *w, int count, int64_t lo, int64_t hi, int *image_off)
+{
+    int off = 0;
+    for (int i = 0; i < count; ++i) {
+        if (lo >= w[i].first_col && hi <= (int64_t)w[i].first_col + w[i].cols) {
+            *image_off = off;
+            return i;
+        }
+        off += w[i].cols;
+    }
+    return -1;
+}
+
+// band set `b` (set `index`: 0 the primary, 1 ... the extras) in image coordinates, or RO_ERR_INVALID
+int move_set(const ro_band_window_t *w, int count, const ro_bands_t &b, int index, ro_bands_t &out)
+{
+    const SetReads r = set_reads(b);
+    int off_n = 0, off_d = 0;
+    const int wn = window_of(w, count, r.noise_lo, r.noise_hi, &off_n);
+    if (wn < 0)
+        return fail(RO_ERR_INVALID, "records of band set %d need its noise band, columns [%lld,%lld), inside one window",
+                    index, (long long)r.noise_lo, (long long)r.noise_hi);
+    const int wd = window_of(w, count, r.detect_lo, r.detect_hi, &off_d);
+    if (wd < 0)
+        return fail(RO_ERR_INVALID, "records of band set %d need its detect band and the average's margin, columns "
+                                    "[%lld,%lld), inside one window", index, (long long)r.detect_lo, (long long)r.detect_hi);
+    out = b;
+    out.low_noise = b.low_noise - w[wn].first_col + off_n;
+    out.low_detect = b.low_detect - w[wd].first_col + off_d;
+    return RO_OK;
+}
+
+// 0: valid; otherwise why not (total: the columns in all, also when they are too many)
+const char *windows_fault(int bins, const ro_band_window_t *w, int count, int64_t *total)
+{
+    *total = 0;
+    if (!w) return "null windows";
+    if (count < 1 || count > RO_MAX_BAND_WINDOWS) return "a call takes 1 ... 8 windows";
+    for (int i = 0; i < count; ++i) {
+        if (w[i].cols < 1) return "every window needs at least one column";
+        if (w[i].first_col < 0 || (int64_t)w[i].first_col + w[i].cols > bins) return "a window lies outside the row";
+        if (i > 0 && w[i].first_col < (int64_t)w[i - 1].first_col + w[i - 1].cols)
+            return "the windows must be ascending and must not overlap";
+        *total += w[i].cols;
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" int ro_stft_band_windows_supported(int bins, const ro_band_window_t *w, int count, int precision)
+{
+    int64_t total = 0;
+    if (bins < 1 || windows_fault(bins, w, count, &total) || total > 1024) return 0;
+    return ro_stft_band_supported_precision(bins, (int)total, precision);
+}
+
+extern "C" int ro_bands_windows(const ro_bands_t *sets, int set_count, int bins, int tile_first_col, int tile_cols,
+                                ro_band_window_t *windows_out, int *count_out)
+{
+    if (!sets || !windows_out || !count_out) return fail(RO_ERR_INVALID, "ro_bands_windows: null argument");
+    if (set_count < 1 || set_count > 1 + RO_MAX_EXTRA_BANDS)
+        return fail(RO_ERR_INVALID, "%d band sets: 1 ... %d (a primary and its extras)", set_count, 1 + RO_MAX_EXTRA_BANDS);
+    if (tile_cols < 0) return fail(RO_ERR_INVALID, "tile_cols must not be negative");
+    std::vector<std::pair<int64_t, int64_t>> iv;        // [lo, hi)
+    for (int i = 0; i < set_count; ++i) {
+        const ro_bands_t &b = sets[i];
+        if (b.noise_width <= 0 || b.detect_width <= 0 || b.avg_bins <= 0)
+            return fail(RO_ERR_INVALID, "bands: widths and avg_bins must be positive");
+        const SetReads r = set_reads(b);
+        iv.emplace_back(r.noise_lo, r.noise_hi);
+        iv.emplace_back(r.detect_lo, r.detect_hi);
+    }
+    if (tile_cols > 0) iv.emplace_back(tile_first_col, (int64_t)tile_first_col + tile_cols);
+    for (const auto &x : iv)
+        if (x.first < 0 || x.second > bins)
+            return fail(RO_ERR_INVALID, "what the recorders read, columns [%lld,%lld), leaves the row [0,%d)",
+                        (long long)x.first, (long long)x.second, bins);
+    std::sort(iv.begin(), iv.end());
+    std::vector<std::pair<int64_t, int64_t>> m;
+    for (const auto &x : iv) {
+        if (!m.empty() && x.first <= m.back().second) m.back().second = std::max(m.back().second, x.second);
+        else m.push_back(x);
+    }
+    while ((int)m.size() > RO_MAX_BAND_WINDOWS) {       // the smallest gap goes; the lower pair on a tie
+        size_t best = 0;
+        for (size_t i = 1; i + 1 < m.size(); ++i)
+            if (m[i + 1].first - m[i].second < m[best + 1].first - m[best].second) best = i;
+        m[best].second = m[best + 1].second;
+        m.erase(m.begin() + (std::ptrdiff_t)best + 1);
+    }
+    for (size_t i = 0; i < m.size(); ++i) {
+        windows_out[i].first_col = (int32_t)m[i].first;
+        windows_out[i].cols = (int32_t)(m[i].second - m[i].first);
+    }
+    *count_out = (int)m.size();
+    return RO_OK;
+}
+
+extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
+                                     int64_t rows, int first_col, int cols, float *d_band, int64_t band_stride,
+                                     ro_scan_record_t *d_records, void *stream)
+{
+    int rc = check_band_handle(h, format);
+    if (rc != RO_OK) return rc;
     ro::BandPlan p{};
     ro::Band64Plan p64{};
     if (h->f64 ? !ro::band64_plan(h->bins, cols, p64) : !ro::band_plan(h->bins, cols, p))
@@ -1093,7 +1248,7 @@ extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format,
     if (d_records) {
         if (!h->cfg.enable_scan) return fail(RO_ERR_INVALID, "records requested but enable_scan == 0");
         int lo = 0, n = 0;
-        const int rc = ro_bands_hull(&h->cfg.bands, h->bins, 0, 0, &lo, &n);
+        rc = ro_bands_hull(&h->cfg.bands, h->bins, 0, 0, &lo, &n);
         if (rc != RO_OK) return rc;
         if (lo < first_col || lo + n > first_col + cols)
             return fail(RO_ERR_INVALID, "records need columns [%d,%d) (the bands and the average's margin); the band is [%d,%d)",
@@ -1105,22 +1260,77 @@ extern "C" int ro_stft_band_resident(ro_stft_t *h, const void *d_iq, int format,
         sc.low_noise -= first_col;
         sc.low_detect -= first_col;
     }
-    if (rows == 0) return RO_OK;
-    if (!d_iq) return fail(RO_ERR_INVALID, "null input pointer");
-    if (!d_band) return fail(RO_ERR_INVALID, "d_band is required");
-    const int64_t last = (first_row + rows - 1) * (int64_t)h->hop + h->bins;
-    if (last > samples)
-        return fail(RO_ERR_INVALID, "rows [%lld,+%lld) need %lld samples, buffer holds %lld", (long long)first_row,
-                    (long long)rows, (long long)last, (long long)samples);
-    if (rows > (int64_t)0x0fffffff) return fail(RO_ERR_INVALID, "too many rows in one launch");
+    bool go = false;
+    rc = check_band_input(h, d_iq, samples, first_row, rows, d_band, &go);
+    if (!go) return rc;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     const ro::ScanArgs *scan = d_records ? &sc : nullptr;
+    const ro_band_window_t one = {first_col, cols};
     if (h->f64)
-        return run_band<ro::Band64Args>(h, h->band64, p64, ro::launch_band64, d_iq, format, first_row, rows, first_col, cols,
-                                        d_band, band_stride, scan, s);
-    return run_band<ro::BandArgs>(h, h->band, p, ro::launch_band, d_iq, format, first_row, rows, first_col, cols, d_band,
-                                  band_stride, scan, s);
+        return run_band<ro::Band64Args>(h, h->band64, p64, ro::launch_band64, d_iq, format, first_row, rows, &one, 1, cols,
+                                        d_band, band_stride, scan, nullptr, s);
+    return run_band<ro::BandArgs>(h, h->band, p, ro::launch_band, d_iq, format, first_row, rows, &one, 1, cols, d_band,
+                                  band_stride, scan, nullptr, s);
+}
+
+extern "C" int ro_stft_band_windows_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
+                                             int64_t rows, const ro_band_window_t *w, int count, float *d_band,
+                                             int64_t band_stride, ro_scan_record_t *d_records, ro_scan_record_t *d_extra,
+                                             void *stream)
+{
+    int rc = check_band_handle(h, format);
+    if (rc != RO_OK) return rc;
+    int64_t total = 0;
+    if (const char *why = windows_fault(h->bins, w, count, &total))
+        return fail(RO_ERR_INVALID, "band windows: %s (%d windows of a %d-bin row)", why, count, h->bins);
+    ro::BandPlan p{};
+    ro::Band64Plan p64{};
+    if (total > 1024 || (h->f64 ? !ro::band64_plan(h->bins, (int)total, p64) : !ro::band_plan(h->bins, (int)total, p)))
+        return fail(RO_ERR_UNSUPPORTED, "no band kernel for %lld columns of %d bins (bins a power of two %d ... 1048576, "
+                                        "1 ... 1024 columns in all)", (long long)total, h->bins, h->f64 ? 131072 : 16384);
+    const int cols = (int)total;
+    if (band_stride < cols)
+        return fail(RO_ERR_INVALID, "band_stride %lld < the windows' %d columns", (long long)band_stride, cols);
+    if (rows < 0 || first_row < 0) return fail(RO_ERR_INVALID, "negative row range");
+    // the scan kernels of the full rows on the band image: the image is their row, each band moves to where its window
+    // sits in it (peak counts from low_detect and stays what it is)
+    ro::ScanArgs sc{};
+    ro::ScanSetsArgs ss{};
+    if (d_records) {
+        if (!h->cfg.enable_scan) return fail(RO_ERR_INVALID, "records requested but enable_scan == 0");
+        ro_bands_t moved{};
+        rc = move_set(w, count, h->cfg.bands, 0, moved);
+        if (rc != RO_OK) return rc;
+        sc = make_scan_args(h, d_band, band_stride, rows, d_records);
+        sc.bins = cols;
+        sc.low_noise = moved.low_noise;
+        sc.low_detect = moved.low_detect;
+    }
+    if (d_extra) {
+        // (extra sets exist only on a handle that scans: ro_stft_set_extra_bands refuses them without enable_scan, so
+        // extra_count > 0 implies it, as on the full path)
+        if (h->extra_count == 0)
+            return fail(RO_ERR_STATE, "extra records requested but no extra band sets are set (ro_stft_set_extra_bands)");
+        ss = make_scan_sets_args(h, d_band, band_stride, rows, d_extra);
+        ss.bins = cols;
+        for (int i = 0; i < h->extra_count; ++i) {
+            rc = move_set(w, count, h->extra[i], 1 + i, ss.sets[i]);
+            if (rc != RO_OK) return rc;
+        }
+    }
+    bool go = false;
+    rc = check_band_input(h, d_iq, samples, first_row, rows, d_band, &go);
+    if (!go) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ro::ScanArgs *scan = d_records ? &sc : nullptr;
+    const ro::ScanSetsArgs *sets = d_extra ? &ss : nullptr;
+    if (h->f64)
+        return run_band<ro::Band64WinArgs>(h, h->band64, p64, ro::launch_band64_windows, d_iq, format, first_row, rows, w,
+                                           count, cols, d_band, band_stride, scan, sets, s);
+    return run_band<ro::BandWinArgs>(h, h->band, p, ro::launch_band_windows, d_iq, format, first_row, rows, w, count, cols,
+                                     d_band, band_stride, scan, sets, s);
 }
 
 extern "C" int ro_stft_time_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples,

@@ -12,12 +12,17 @@ Prints, per shape: rows/s of each leg with the spread of the five repeats, the r
 the band's algorithmic bytes (hop x 8 + cols x 4 per row) make in (b), and the worst parity figure of both legs on the
 first 8 rows (max |x - oracle| / max of the full oracle row).
 
-    python tools/band/bench_band.py [--window 0.5] [--repeats 5] [--precision f32|f64]
+    python tools/band/bench_band.py [--window 0.5] [--repeats 5] [--precision f32|f64] [--windows]
 
 --precision f64: both legs on an RO_PRECISION_F64 handle, where (a) with tile = band is the only other way to serve the
 consumer in the reference's arithmetic.  Shapes: Ionozor's doppler configuration as above, and 131072 / 98304, 2048 rows,
 the 777-column hull of Bolidozor's bands at that size, with records.  The parity figure becomes per-bin:
 max |x - oracle| / oracle over the band's bins of the first 8 rows.
+
+--windows: the window-list call at the flagship shape, radio-observer.json (32768 / 24576, 4096 rows), whose hull of
+1365 columns band_resident refuses: (a) as above with the 615-column snapshot tile and records, (b) band_windows_resident
+over the windows ro_bands_windows gives for the bands and that tile (the noise band; the detect band with the tile), with
+records.  Parity of (b) is taken on the tile's columns of its image and on the whole image.
 """
 import argparse
 import importlib
@@ -67,11 +72,18 @@ def timed(torch, launch, window_s):
     return total / iters, total
 
 
-def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, args, f64=False):
+def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, args, f64=False, windows=None):
+    """windows (a list of (first_col, cols)): leg (b) is band_windows_resident over them; `band` is then the one of them
+    that gets the signal's in-band tone"""
     hop = bins - overlap
     first_col, cols = band
+    if windows is not None:
+        cols = sum(n for _, n in windows)
+        take = np.concatenate([np.arange(f, f + n) for f, n in windows])
+    else:
+        take = np.arange(first_col, first_col + cols)
     samples = (rows - 1) * hop + bins
-    iq = make_stream(torch, samples, bins, fs, first_col, cols, seed=bins)
+    iq = make_stream(torch, samples, bins, fs, band[0], band[1], seed=bins)
     d_rows = torch.empty((rows, bins), dtype=torch.float32, device="cuda")
     d_tile = torch.empty((rows, tile[1]), dtype=torch.float32, device="cuda")
     d_band = torch.empty((rows, cols), dtype=torch.float32, device="cuda")
@@ -84,7 +96,10 @@ def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, a
             st.run_resident(iq, ro.RO_IQ_F32, samples, 0, rows, d_rows, d_tile=d_tile, d_records=rec_a, stream=stream)
 
         def leg_b():
-            st.band_resident(iq, ro.RO_IQ_F32, samples, 0, rows, first_col, cols, d_band, d_records=rec_b, stream=stream)
+            if windows is not None:
+                st.band_windows_resident(iq, ro.RO_IQ_F32, samples, 0, rows, windows, d_band, d_records=rec_b, stream=stream)
+            else:
+                st.band_resident(iq, ro.RO_IQ_F32, samples, 0, rows, first_col, cols, d_band, d_records=rec_b, stream=stream)
 
         for _ in range(2):                                              # warm-up: tables, scratch, clocks
             leg_a()
@@ -102,9 +117,9 @@ def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, a
     want = oracle.stft(iq[:(n8 - 1) * hop + bins].cpu().numpy(), bins, overlap, max_rows=n8).astype(np.float64)
     ref = want.max(axis=1)
     err_a = (np.abs(d_tile[:n8].cpu().numpy() - want[:, tile[0]:tile[0] + tile[1]]).max(axis=1) / ref).max()
-    err_b = (np.abs(d_band[:n8].cpu().numpy() - want[:, first_col:first_col + cols]).max(axis=1) / ref).max()
+    err_b = (np.abs(d_band[:n8].cpu().numpy() - want[:, take]).max(axis=1) / ref).max()
     if f64:                                                             # per bin, on the band's bins
-        wa, wb = want[:, tile[0]:tile[0] + tile[1]], want[:, first_col:first_col + cols]
+        wa, wb = want[:, tile[0]:tile[0] + tile[1]], want[:, take]
         err_a = (np.abs(d_tile[:n8].cpu().numpy() - wa) / wa).max()
         err_b = (np.abs(d_band[:n8].cpu().numpy() - wb) / wb).max()
     same_peaks = ""
@@ -115,8 +130,10 @@ def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, a
     alg = hop * 8 + cols * 4
     spread = lambda x: (x.max() - x.min()) / np.median(x)
     ratio = np.median(tb) / np.median(ta)
-    print("%s: %d bins / overlap %d, %d rows, band [%d,+%d), tile [%d,+%d), shortest window %.2f s" %
-          (name, bins, overlap, rows, first_col, cols, tile[0], tile[1], shortest))
+    what = "band [%d,+%d)" % (first_col, cols) if windows is None else \
+        "windows %s (%d columns)" % (" ".join("[%d,+%d)" % w for w in windows), cols)
+    print("%s: %d bins / overlap %d, %d rows, %s, tile [%d,+%d), shortest window %.2f s" %
+          (name, bins, overlap, rows, what, tile[0], tile[1], shortest))
     print("  (a) full rows + tile%s: median %10.0f rows/s  (min %.0f, max %.0f, spread %.1f %%)" %
           (" + records" if bands is not None else "", np.median(ta), ta.min(), ta.max(), 100 * spread(ta)))
     print("  (b) band only%s:        median %10.0f rows/s  (min %.0f, max %.0f, spread %.1f %%)" %
@@ -126,6 +143,11 @@ def shape(torch, ro, oracle, name, bins, overlap, fs, rows, bands, tile, band, a
           (alg, alg * np.median(tb) / 1e9, alg * np.median(tb) / 1e9 / HBM_PEAK_GBS, HBM_PEAK_GBS))
     print("  parity on the first %d rows, max err / %s: (a) %.2e  (b) %.2e%s" %
           (n8, "oracle, per bin" if f64 else "full row max", err_a, err_b, same_peaks))
+    if windows is not None:                                             # the tile's columns, cut from (b)'s image
+        at = int(np.searchsorted(take, tile[0]))
+        assert (take[at:at + tile[1]] == np.arange(tile[0], tile[0] + tile[1])).all()
+        err_t = (np.abs(d_band[:n8, at:at + tile[1]].cpu().numpy() - want[:, tile[0]:tile[0] + tile[1]]).max(axis=1) / ref).max()
+        print("  (b) on the tile's columns alone: %.2e" % err_t)
     return tb.min() > ta.max()
 
 
@@ -149,18 +171,38 @@ def main_f64(torch, ro, oracle, args):
     return 0
 
 
+def main_windows(torch, ro, oracle, args):
+    # radio-observer.json:62-87 (bands) and the snapshot's 10100 ... 11000 Hz
+    bins, overlap, fs = 32768, 24576, 48000
+    b = oracle.bolid_bands(bins, fs, overlap, 10300, 10900, 9000, 9600, 2, 5, 40)
+    bands = ro.Bands(low_noise=b.low_noise, noise_width=b.noise_width, low_detect=b.low_detect,
+                     detect_width=b.detect_width, avg_bins=b.avg_bins)
+    t0, t1 = ro.frequency_to_bin(bins, fs, 10100.0), ro.frequency_to_bin(bins, fs, 11000.0)
+    tile = (t0, t1 - t0)
+    windows = [(w.first_col, w.cols) for w in ro.bands_windows(bands, bins, *tile)]
+    hull = ro.bands_hull(bands, bins, *tile)
+    assert ro.band_windows_supported(bins, windows) and not ro.band_supported(bins, hull[1])
+    faster = shape(torch, ro, oracle, "radio-observer.json, window list", bins, overlap, fs, max(8, int(4096 * args.rows_scale)),
+                   bands, tile, windows[-1], args, windows=windows)
+    print("window list faster than full rows by more than the repeats' spread: %s" % ("yes" if faster else "NO"))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=0.5, help="seconds of launches per timed leg, at least")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--rows-scale", type=float, default=1.0, help="scale both row counts (quick runs)")
     ap.add_argument("--precision", choices=("f32", "f64"), default="f32", help="precision of the handle both legs run on")
+    ap.add_argument("--windows", action="store_true", help="the window-list call at radio-observer.json's shape, nothing else")
     args = ap.parse_args()
     import torch
     ro = importlib.import_module("radio-observer_amd")
     import ro_oracle as oracle
     oracle.lib()
     ok = True
+    if args.windows:
+        return main_windows(torch, ro, oracle, args)
     if args.precision == "f64":
         return main_f64(torch, ro, oracle, args)
     # Bolidozor.json:45-46, :75-76 (snapshot columns), :84-93 (bands; avg_freq_range at its default of 40 Hz)
