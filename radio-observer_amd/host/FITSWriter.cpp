@@ -91,7 +91,9 @@ void FITSWriter::date()
 {
     std::time_t now = std::time(nullptr);
     char b[32];
-    std::strftime(b, sizeof(b), "%Y-%m-%dT%H:%M:%S", std::gmtime(&now));
+    std::tm parts;                                      // (gmtime_r: the worker thread writes files while the stream's
+    gmtime_r(&now, &parts);                             // thread formats names; std::gmtime shares one struct tm)
+    std::strftime(b, sizeof(b), "%Y-%m-%dT%H:%M:%S", &parts);
     writeHeader("DATE", b, "file creation date (YYYY-MM-DDThh:mm:ss UT)");
 }
 

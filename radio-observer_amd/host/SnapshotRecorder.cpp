@@ -15,7 +15,11 @@ static std::string formatTime(const WFTime &t, const char *fmt)       // src/WFT
 {
     std::time_t s = (std::time_t)t.sec;
     char buf[256];
-    const size_t n = std::strftime(buf, sizeof(buf), fmt, std::gmtime(&s));
+    // gmtime_r: update() names the next snapshot on the stream's thread while the worker stamps the file it is writing;
+    // std::gmtime's shared struct tm let one tear the other's fields (a name with the worker's hour, minute and second)
+    std::tm parts;
+    gmtime_r(&s, &parts);
+    const size_t n = std::strftime(buf, sizeof(buf), fmt, &parts);
     return std::string(buf, n);
 }
 
