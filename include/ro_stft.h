@@ -396,6 +396,54 @@ int ro_stft_band_windows_resident(ro_stft_t *h, const void *d_iq, int format, in
                                   float *d_band, int64_t band_stride,
                                   ro_scan_record_t *d_records, ro_scan_record_t *d_extra, void *stream);
 
+/* ---- tile windows: up to 8 column windows cut from each FULL row ---------------
+ * WaterfallBackend keeps a vector of recorders and every SnapshotRecorder / BolidRecorder cuts its own [leftBin,
+ * rightBin) out of each row (src/WaterfallBackend.cpp:174-205, :368-374).  A handle's one tile (tile_first_col,
+ * tile_cols) can only serve them with the hull of everything.  A TILE WINDOW is a run of columns [first_col, first_col +
+ * cols) of the fft-shifted row (ro_band_window_t); the calls below copy up to RO_MAX_TILE_WINDOWS of them out of full rows
+ * into the IMAGE ro_stft_band_windows_resident defines: window w occupies floats [off_w, off_w + cols_w) of each image
+ * row, off_w the sum of the earlier windows' cols; floats past the total in a row are never touched.  The rows come from
+ * the full-row transform, so there is no cap on the total other than bins (radio-observer.json's bolid event band alone
+ * is 2048 columns), every size, precision and format of ro_stft_run_resident is served, and a host may choose between
+ * this and the band call by shape: the layout is the same. */
+#define RO_MAX_TILE_WINDOWS 8
+
+/* 1 if ro_bins_supported(bins) (chirp-z lengths included), 1 <= count <= RO_MAX_TILE_WINDOWS, every cols >= 1, every
+ * window inside [0, bins), ascending and not overlapping (touching is allowed); else 0.  Pure host. */
+int ro_tile_windows_supported(int bins, const ro_band_window_t *windows, int count);
+
+/* The tile windows of a host with several recorders (src/WaterfallBackend.cpp:174-205, :368-374: each recorder's
+ * [leftBin, rightBin)).  ranges: 1 <= range_count <= 32 column ranges, any order, overlaps allowed.  Ranges that overlap
+ * or touch are merged; while more than RO_MAX_TILE_WINDOWS remain, the pair with the smallest gap is merged (the lower
+ * pair on a tie) -- ro_bands_windows' rule.  windows_out: RO_MAX_TILE_WINDOWS entries, ascending, *count_out of them
+ * written; they pass ro_tile_windows_supported wherever bins does.  offsets_out (range_count entries, may be NULL):
+ * offsets_out[i] is the image column where ranges[i].first_col sits, so recorder i reads image columns [offsets_out[i],
+ * + ranges[i].cols).  RO_ERR_INVALID for a range that leaves [0, bins), for cols < 1, for a count out of range.
+ * Pure host. */
+int ro_merge_windows(const ro_band_window_t *ranges, int range_count, int bins,
+                     ro_band_window_t *windows_out, int *count_out, int32_t *offsets_out);
+
+/* The windows' columns of `rows` rows that are already in HBM (like ro_stft_scan_resident): d_rows, rows x row_stride
+ * floats (row_stride >= bins); d_image, rows x image_stride floats (image_stride >= the windows' total).  The image
+ * equals d_rows[:, columns] exactly; a plain copy, each wanted float read once and written once.  rows == 0 is RO_OK
+ * and writes nothing.  RO_ERR_INVALID for null pointers, image_stride < total, and a window list
+ * ro_tile_windows_supported refuses (the message names the offending window).  Asynchronous on `stream`. */
+int ro_stft_cut_windows_resident(ro_stft_t *h, const float *d_rows, int64_t row_stride, int64_t rows,
+                                 const ro_band_window_t *windows, int count,
+                                 float *d_image, int64_t image_stride, void *stream);
+
+/* ro_stft_run_resident_sets with d_tile = NULL, then ro_stft_cut_windows_resident of the same rows on the same stream:
+ * the rows, d_records and d_extra are the bits ro_stft_run_resident_sets gives (the records are scanned on the full
+ * row, in row coordinates -- not image coordinates as in ro_stft_band_windows_resident), the image is those rows'
+ * columns.  Every handle ro_stft_run_resident works on: any plan, float32 and RO_PRECISION_F64, chirp-z lengths, the
+ * chunked paths.  A handle's configured tile is simply not produced by this call.  d_records / d_extra may be NULL.
+ * Refusals as ro_stft_run_resident_sets and ro_stft_cut_windows_resident.  Asynchronous on `stream`. */
+int ro_stft_run_resident_windows(ro_stft_t *h, const void *d_iq, int format, int64_t samples,
+                                 int64_t first_row, int64_t rows, float *d_rows, int64_t row_stride,
+                                 const ro_band_window_t *windows, int count,
+                                 float *d_image, int64_t image_stride,
+                                 ro_scan_record_t *d_records, ro_scan_record_t *d_extra, void *stream);
+
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel
  * when records are requested).  kernel_ms_out (optional, 2 floats) receives the
@@ -432,6 +480,17 @@ int ro_stft_fetch(ro_stft_t *h, int64_t max_rows, int first_col, int cols,
 int ro_stft_fetch_sets(ro_stft_t *h, int64_t max_rows, int first_col, int cols, float *rows_out,
                        ro_scan_record_t *records_out, ro_scan_record_t *extra_out,
                        int64_t *first_row_index, int64_t *rows_got);
+/* Tile windows on the streaming path: with windows set, each batch's rows are cut (ro_stft_cut_windows_resident's
+ * kernel) behind the transform and only the image and the records travel to the host -- the recorders' own [leftBin,
+ * rightBin) cuts (src/WaterfallBackend.cpp:174-205, :368-374) instead of full rows or one tile over their hull.
+ * first_col / cols of ro_stft_fetch and ro_stft_fetch_sets are then IMAGE columns in [0, total), RO_ERR_INVALID outside;
+ * the records stay those of the full row, in row coordinates.  count = 0 removes the windows and restores full rows.
+ * The list is checked like ro_tile_windows_supported (RO_ERR_INVALID, the message names the offending window).  Only on
+ * an idle stream (nothing staged, nothing waiting to be fetched), else RO_ERR_STATE; the slots' image blocks and the
+ * pinned batches start over.  Refused: a handle created with a tile (tile_cols > 0) or tile_ln, RO_ERR_UNSUPPORTED; a
+ * handle with a row sink, RO_ERR_STATE -- and ro_stft_set_row_sink gives RO_ERR_STATE while windows are set. */
+int ro_stft_set_tile_windows(ro_stft_t *h, const ro_band_window_t *windows, int count);
+int ro_stft_tile_windows(const ro_stft_t *h, ro_band_window_t *out /* may be NULL */);   /* returns count */
 /* Rows at the head of the output queue whose batches have finished on the device, download included: ro_stft_fetch
  * hands these over without waiting (it WAITS for anything beyond them).  A host that fetches only what is complete
  * keeps the next batch in flight under the previous one's download and under its own per-row work -- the recorders

@@ -16,6 +16,7 @@ RO_IQ_F32, RO_IQ_I16, RO_IQ_F64 = 0, 1, 2
 RO_PRECISION_F32, RO_PRECISION_F64 = 0, 1
 RO_MAX_EXTRA_BANDS = 7
 RO_MAX_BAND_WINDOWS = 8
+RO_MAX_TILE_WINDOWS = 8
 
 RO_OK = 0
 _ERR_NAMES = {-1: "RO_ERR_INVALID", -2: "RO_ERR_UNSUPPORTED", -3: "RO_ERR_HIP", -4: "RO_ERR_NOMEM",
@@ -139,6 +140,16 @@ _EXPORTS = {
     "ro_stft_band_windows_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                                 C.POINTER(BandWindow), C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
+    "ro_tile_windows_supported": (C.c_int, [C.c_int, C.POINTER(BandWindow), C.c_int]),
+    "ro_merge_windows": (C.c_int, [C.POINTER(BandWindow), C.c_int, C.c_int, C.POINTER(BandWindow), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int32)]),
+    "ro_stft_cut_windows_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BandWindow),
+                                               C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ro_stft_run_resident_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_int64, C.POINTER(BandWindow), C.c_int, C.c_void_p,
+                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ro_stft_set_tile_windows": (C.c_int, [C.c_void_p, C.POINTER(BandWindow), C.c_int]),
+    "ro_stft_tile_windows": (C.c_int, [C.c_void_p, C.POINTER(BandWindow)]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -359,6 +370,24 @@ def bands_windows(sets, bins, tile_first_col=0, tile_cols=0):
     return [BandWindow(out[i].first_col, out[i].cols) for i in range(n.value)]
 
 
+def tile_windows_supported(bins, windows):
+    """whether these windows (BandWindow or (first_col, cols) each) can be cut from a `bins`-bin full row: 1 ... 8 of
+    them, ascending, not overlapping, inside the row -- ro_tile_windows_supported"""
+    arr, n = _windows(windows)
+    return bool(library().ro_tile_windows_supported(bins, arr, n))
+
+
+def merge_windows(ranges, bins):
+    """(windows, offsets): the tile windows (a list of BandWindow, ascending, at most 8) that hold the recorders' column
+    ranges `ranges` (1 ... 32 of BandWindow or (first_col, cols), any order, overlaps allowed), and for each range the
+    image column where its first column sits -- ro_merge_windows"""
+    arr, n = _windows(ranges)
+    out, count = (BandWindow * RO_MAX_TILE_WINDOWS)(), C.c_int()
+    offs = (C.c_int32 * max(n, 1))()
+    _check(library().ro_merge_windows(arr, n, bins, out, C.byref(count), offs))
+    return [BandWindow(out[i].first_col, out[i].cols) for i in range(count.value)], [int(offs[i]) for i in range(n)]
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -415,6 +444,7 @@ class Stft:
         self.scan_enabled = bands is not None
         self.tile = tile
         self.extra_count = 0
+        self.image_cols = 0                              # columns of the tile windows' image (0: no windows set)
         if extra_bands:
             try:
                 self.set_extra_bands(extra_bands)
@@ -533,6 +563,25 @@ class Stft:
                                                        _ptr(d_band), band_stride or total, _ptr(d_records),
                                                        _ptr(d_extra), _ptr(stream)))
 
+    def cut_windows_resident(self, d_rows, rows, windows, d_image, row_stride=None, image_stride=None, stream=None):
+        """the columns of `windows` (BandWindow or (first_col, cols) each, ascending) of rows already in HBM, side by
+        side in rows x image_stride float32 -- ro_stft_cut_windows_resident"""
+        arr, n = _windows(windows)
+        total = sum(arr[i].cols for i in range(n))
+        _check(library().ro_stft_cut_windows_resident(self._h, _ptr(d_rows), row_stride or self.bins, rows, arr, n,
+                                                      _ptr(d_image), image_stride or total, _ptr(stream)))
+
+    def run_resident_windows(self, d_iq, fmt, samples, first_row, rows, d_rows, windows, d_image, row_stride=None,
+                             image_stride=None, d_records=None, d_extra=None, stream=None):
+        """run_resident_sets without a tile, then the columns of `windows` of those rows side by side in rows x
+        image_stride float32; the records are the full rows', in row coordinates -- ro_stft_run_resident_windows"""
+        arr, n = _windows(windows)
+        total = sum(arr[i].cols for i in range(n))
+        _check(library().ro_stft_run_resident_windows(self._h, _ptr(d_iq), fmt, samples, first_row, rows, _ptr(d_rows),
+                                                      row_stride or self.bins, arr, n, _ptr(d_image),
+                                                      image_stride or total, _ptr(d_records), _ptr(d_extra),
+                                                      _ptr(stream)))
+
     def scan_resident(self, d_rows, rows, d_records, row_stride=None, stream=None):
         _check(library().ro_stft_scan_resident(self._h, _ptr(d_rows), row_stride or self.bins, rows,
                                                _ptr(d_records), _ptr(stream)))
@@ -577,11 +626,33 @@ class Stft:
         _check(library().ro_stft_flush(self._h, C.byref(ready)))
         return ready.value
 
-    def fetch(self, max_rows, first_col=None, cols=None, want_records=None):
-        if first_col is None:                        # default: everything this handle brings to the host
-            first_col = self.tile[0] if self.tile else 0
+    def set_tile_windows(self, windows):
+        """up to RO_MAX_TILE_WINDOWS column windows (BandWindow or (first_col, cols) each, ascending) cut from every
+        row of the streaming path: only their image travels to the host, and fetch / fetch_sets count in image columns;
+        an empty list restores full rows -- ro_stft_set_tile_windows"""
+        arr, n = _windows(windows or [])
+        _check(library().ro_stft_set_tile_windows(self._h, arr, n))
+        self.image_cols = sum(arr[i].cols for i in range(n))
+
+    @property
+    def tile_windows(self):
+        arr = (BandWindow * RO_MAX_TILE_WINDOWS)()
+        n = library().ro_stft_tile_windows(self._h, arr)
+        if n < 0:
+            _check(n)
+        return [BandWindow(arr[i].first_col, arr[i].cols) for i in range(n)]
+
+    def _default_columns(self, first_col, cols):
+        """everything this handle brings to the host: the tile windows' image, the tile, or the full row"""
+        lo, n = (0, self.image_cols) if self.image_cols else self.tile if self.tile else (0, self.bins)
+        if first_col is None:
+            first_col = lo
         if cols is None:
-            cols = (self.tile[0] + self.tile[1] - first_col) if self.tile else self.bins - first_col
+            cols = lo + n - first_col
+        return first_col, cols
+
+    def fetch(self, max_rows, first_col=None, cols=None, want_records=None):
+        first_col, cols = self._default_columns(first_col, cols)
         want_records = self.scan_enabled if want_records is None else want_records
         rows = np.empty((max_rows, cols), dtype=np.float32)
         recs = np.empty(max_rows, dtype=SCAN_DTYPE) if want_records else None
@@ -597,10 +668,7 @@ class Stft:
     def fetch_sets(self, max_rows, first_col=None, cols=None, want_rows=None, want_extra=True):
         """ro_stft_fetch_sets: (first_row_index, rows, records, extra) with extra shaped (rows_got, extra_count); rows is
         None for a handle with a row sink (they are in the ring), records None without a primary set"""
-        if first_col is None:
-            first_col = self.tile[0] if self.tile else 0
-        if cols is None:
-            cols = (self.tile[0] + self.tile[1] - first_col) if self.tile else self.bins - first_col
+        first_col, cols = self._default_columns(first_col, cols)
         want_rows = (getattr(self, "_sink", None) is None) if want_rows is None else want_rows
         rows = np.empty((max_rows, cols), dtype=np.float32) if want_rows else None
         recs = np.empty(max_rows, dtype=SCAN_DTYPE) if self.scan_enabled else None

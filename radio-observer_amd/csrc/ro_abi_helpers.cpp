@@ -43,6 +43,51 @@ void build_window(int kind, int bins, float *w)
     }
 }
 
+// tile windows: nullptr if the list is valid, otherwise why not (*which: the offending window, -1: the list itself);
+// *total: the columns in all
+const char *tile_windows_fault(int bins, const ro_band_window_t *w, int count, int64_t *total, int *which)
+{
+    *total = 0;
+    *which = -1;
+    if (!w) return "null windows";
+    if (count < 1 || count > RO_MAX_TILE_WINDOWS) return "a call takes 1 ... 8 windows";
+    for (int i = 0; i < count; ++i) {
+        *which = i;
+        if (w[i].cols < 1) return "needs at least one column";
+        if (w[i].first_col < 0 || (int64_t)w[i].first_col + w[i].cols > bins) return "lies outside the row";
+        if (i > 0 && w[i].first_col < (int64_t)w[i - 1].first_col + w[i - 1].cols)
+            return "starts before the one in front of it ends (ascending, not overlapping)";
+        *total += w[i].cols;
+    }
+    *which = -1;
+    return nullptr;
+}
+
+// the same as a refusal: RO_ERR_INVALID, the message names the offending window
+int tile_windows_check(const char *who, int bins, const ro_band_window_t *w, int count, int64_t *total)
+{
+    int which = -1;
+    const char *why = tile_windows_fault(bins, w, count, total, &which);
+    if (!why) return RO_OK;
+    if (which < 0) return fail(RO_ERR_INVALID, "%s: %s (%d windows of a %d-bin row)", who, why, count, bins);
+    return fail(RO_ERR_INVALID, "%s: window %d, columns [%d,+%d) of a %d-bin row, %s", who, which, w[which].first_col,
+                w[which].cols, bins, why);
+}
+
+ro::CutArgs make_cut_args(const ro_band_window_t *w, int count, float *d_image, int64_t image_stride)
+{
+    ro::CutArgs c{};
+    c.image = d_image;
+    c.image_stride = image_stride;
+    c.count = count;
+    for (int i = 0; i < count; ++i) {
+        c.first[i] = w[i].first_col;
+        c.off[i] = c.total;
+        c.total += w[i].cols;
+    }
+    return c;
+}
+
 }  // namespace host
 }  // namespace ro
 
@@ -172,6 +217,63 @@ extern "C" int ro_stitch_rows(const void *gathered, int64_t total_rows, int worl
         std::memcpy(dst + (size_t)first * row_bytes, src + (size_t)g * (size_t)block * row_bytes,
                     (size_t)rows * row_bytes);
     }
+    return RO_OK;
+}
+
+// ---------------------------------------------------------------------------
+// tile windows (host arithmetic): what several recorders keep of a row, src/WaterfallBackend.cpp:174-205, :368-374
+// ---------------------------------------------------------------------------
+extern "C" int ro_tile_windows_supported(int bins, const ro_band_window_t *windows, int count)
+{
+    int64_t total = 0;
+    int which = -1;
+    if (bins < 1 || !ro_bins_supported(bins)) return 0;
+    return tile_windows_fault(bins, windows, count, &total, &which) ? 0 : 1;
+}
+
+extern "C" int ro_merge_windows(const ro_band_window_t *ranges, int range_count, int bins, ro_band_window_t *windows_out,
+                                int *count_out, int32_t *offsets_out)
+{
+    if (!ranges || !windows_out || !count_out) return fail(RO_ERR_INVALID, "ro_merge_windows: null argument");
+    if (range_count < 1 || range_count > 32) return fail(RO_ERR_INVALID, "ro_merge_windows: %d ranges: 1 ... 32", range_count);
+    std::vector<std::pair<int64_t, int64_t>> iv;        // [lo, hi)
+    for (int i = 0; i < range_count; ++i) {
+        if (ranges[i].cols < 1)
+            return fail(RO_ERR_INVALID, "ro_merge_windows: range %d has %d columns: at least one", i, ranges[i].cols);
+        if (ranges[i].first_col < 0 || (int64_t)ranges[i].first_col + ranges[i].cols > bins)
+            return fail(RO_ERR_INVALID, "ro_merge_windows: range %d, columns [%d,+%d), leaves the row [0,%d)", i,
+                        ranges[i].first_col, ranges[i].cols, bins);
+        iv.emplace_back(ranges[i].first_col, (int64_t)ranges[i].first_col + ranges[i].cols);
+    }
+    std::sort(iv.begin(), iv.end());
+    std::vector<std::pair<int64_t, int64_t>> m;
+    for (const auto &x : iv) {
+        if (!m.empty() && x.first <= m.back().second) m.back().second = std::max(m.back().second, x.second);
+        else m.push_back(x);
+    }
+    while ((int)m.size() > RO_MAX_TILE_WINDOWS) {       // the smallest gap goes; the lower pair on a tie (ro_bands_windows)
+        size_t best = 0;
+        for (size_t i = 1; i + 1 < m.size(); ++i)
+            if (m[i + 1].first - m[i].second < m[best + 1].first - m[best].second) best = i;
+        m[best].second = m[best + 1].second;
+        m.erase(m.begin() + (std::ptrdiff_t)best + 1);
+    }
+    for (size_t i = 0; i < m.size(); ++i) {
+        windows_out[i].first_col = (int32_t)m[i].first;
+        windows_out[i].cols = (int32_t)(m[i].second - m[i].first);
+    }
+    *count_out = (int)m.size();
+    if (offsets_out)
+        for (int i = 0; i < range_count; ++i) {         // every range lies whole inside exactly one window
+            int64_t off = 0;
+            for (const auto &x : m) {
+                if (ranges[i].first_col >= x.first && ranges[i].first_col < x.second) {
+                    offsets_out[i] = (int32_t)(off + ranges[i].first_col - x.first);
+                    break;
+                }
+                off += x.second - x.first;
+            }
+        }
     return RO_OK;
 }
 

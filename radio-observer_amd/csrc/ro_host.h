@@ -152,8 +152,11 @@ struct ro_stft {
     // extra band sets (ro_stft_set_extra_bands): scanned by ro_scan_sets.hip behind the primary's scan
     ro_bands_t extra[RO_MAX_EXTRA_BANDS] = {};
     int        extra_count = 0;
+    // tile windows of the streaming path (ro_stft_set_tile_windows): cut by ro_cut_windows.hip behind each batch's rows
+    ro_band_window_t tile_win[RO_MAX_TILE_WINDOWS] = {};
+    int        tile_win_count = 0, tile_win_total = 0;
 
-    // streaming state.  Three HIP streams and RO_STREAM_SLOTS slots of device buffers: while the kernels of batch n run on
+    // streaming state. Three HIP streams and RO_STREAM_SLOTS slots of device buffers: while the kernels of batch n run on
     // `stream`, batch n+1 is uploaded on `s_in` and batch n-1 goes home on `s_out`.
     int batch_rows = 0;
     // Samples are staged where the upload reads them: in the pinned buffer (h_in) of the slot the next batch will use
@@ -174,6 +177,7 @@ struct ro_stft {
         DeviceBlock<float> d_minmax;
         DeviceBlock<ro_scan_record_t> d_records;
         DeviceBlock<ro_scan_record_t> d_extra; // batch_rows x extra_count: the extra band sets' records
+        DeviceBlock<float> d_image;            // batch_rows x tile_win_total: the tile windows' image
         PinnedBlock<char> h_in;                // pinned upload staging, bytes
         hipEvent_t uploaded = nullptr;         // H2D of this slot done (h_in reusable, kernels may start)
         hipEvent_t staging_free = nullptr;     // what the host waits for before it writes h_in again: `uploaded`, or the `done`
@@ -273,6 +277,12 @@ namespace host {
 
 // ---- ro_abi_helpers.cpp
 void build_window(int kind, int bins, float *w);
+// tile windows: nullptr if the list is valid, else why not (*which: the offending window, -1: the list itself)
+const char *tile_windows_fault(int bins, const ro_band_window_t *w, int count, int64_t *total, int *which);
+// ... as a refusal (RO_ERR_INVALID, the message names the offending window) in the name of entry point `who`
+int tile_windows_check(const char *who, int bins, const ro_band_window_t *w, int count, int64_t *total);
+// the window list and the image of a cut; rows_in / rows / row_stride are filled in by launch_tile_and_scan
+ro::CutArgs make_cut_args(const ro_band_window_t *w, int count, float *d_image, int64_t image_stride);
 
 // ---- ro_stft_capi.cpp
 ro::StftArgs make_stft_args(const ro_stft *h, const void *d_iq, int64_t first_row, int64_t rows, float *d_rows,
@@ -287,9 +297,10 @@ int launch_transform(ro_stft *h, const void *d_iq, int format, int64_t first_row
                      float *d_ln = nullptr);
 // d_ln / d_minmax: the tile's log and the rows' min / max of it (tile_ln); need d_tile
 // d_extra: rows x extra_count records of the handle's extra band sets (null: nothing is launched for them)
+// cut: tile windows to copy out of these rows behind everything else (make_cut_args; null: none)
 int launch_tile_and_scan(ro_stft *h, const float *d_rows, int64_t row_stride, int64_t rows, float *d_tile,
                          ro_scan_record_t *d_records, hipStream_t s, float *d_ln = nullptr, float *d_minmax = nullptr,
-                         ro_scan_record_t *d_extra = nullptr);
+                         ro_scan_record_t *d_extra = nullptr, const ro::CutArgs *cut = nullptr);
 int check_bands(const ro_stft *h, const ro_bands_t &b);
 int ensure_ln_part(ro_stft *h, int64_t rows);
 int launch_spectra_big(ro_stft *h, const void *d_iq, int format, int64_t first_row, int64_t rows, float2 *d_out,

@@ -91,6 +91,20 @@ struct ScanSetsArgs {
     ro_bands_t        sets[RO_MAX_EXTRA_BANDS];
 };
 
+// up to RO_MAX_TILE_WINDOWS column windows of full rows side by side in one image (ro_cut_windows.hip): a plain copy, the
+// window list in the kernel arguments like the band sets above
+struct CutArgs {
+    const float *rows_in;          // rows x row_stride, row_stride >= every first[w] + cols[w]
+    float       *image;            // rows x image_stride, image_stride >= total
+    int64_t      rows;
+    int64_t      row_stride;
+    int64_t      image_stride;
+    int          count;            // 1 ... RO_MAX_TILE_WINDOWS
+    int          total;            // the windows' columns in all
+    int32_t      first[RO_MAX_TILE_WINDOWS];   // window w: columns [first[w], first[w] + cols of w) of the row ...
+    int32_t      off[RO_MAX_TILE_WINDOWS];     // ... at image columns [off[w], off[w + 1]); off[0] = 0, ascending
+};
+
 // ---- strict precision (RO_PRECISION_F64): the Stockham recurrence as separate radix-16 passes in double, any power of two
 struct BigArgsD {
     const void    *iq;         // FIRST pass: sample 0 of the stream
@@ -227,6 +241,7 @@ void       stft32k_window_layout(const float *w, float *out);         // host: 3
 hipError_t launch_stft_wl(int bins, int fmt, const StftArgs &a, hipStream_t s);
 hipError_t launch_scan(const ScanArgs &a, hipStream_t s);
 hipError_t launch_scan_sets(const ScanSetsArgs &a, hipStream_t s);      // ro_scan_sets.hip
+hipError_t launch_cut_windows(const CutArgs &a, hipStream_t s);         // ro_cut_windows.hip
 hipError_t launch_tile(const TileArgs &a, hipStream_t s);
 hipError_t launch_ln_tile(const LnArgs &a, hipStream_t s);
 // per-row log of a compact tile + min / max (plans without the fused epilogue), and the fold of the fused partials

@@ -304,7 +304,8 @@ ro::StftArgs make_stft_args(const ro_stft *h, const void *d_iq, int64_t first_ro
 
 // d_ln / d_minmax: the tile's log and the rows' min / max of it (tile_ln); need d_tile
 int launch_tile_and_scan(ro_stft *h, const float *d_rows, int64_t row_stride, int64_t rows, float *d_tile,
-                         ro_scan_record_t *d_records, hipStream_t s, float *d_ln, float *d_minmax, ro_scan_record_t *d_extra)
+                         ro_scan_record_t *d_records, hipStream_t s, float *d_ln, float *d_minmax, ro_scan_record_t *d_extra,
+                         const ro::CutArgs *cut)
 {
     const bool want_ln = d_tile && (d_ln || d_minmax);
     if (!h->f64 && ro::stft_fuses_scan(h->bins)) {                  // tile, log and records written by the transform
@@ -317,6 +318,14 @@ int launch_tile_and_scan(ro_stft *h, const float *d_rows, int64_t row_stride, in
     // the extra band sets, from the rows in HBM whatever wrote the primary's record (the fused epilogue is frozen)
     if (d_extra && h->extra_count > 0)
         HIP_TRY(ro::launch_scan_sets(make_scan_sets_args(h, d_rows, row_stride, rows, d_extra), s));
+    // the tile windows, a plain copy out of the rows in HBM for every plan alike (no transform's epilogue knows them)
+    if (cut) {
+        ro::CutArgs c = *cut;
+        c.rows_in = d_rows;
+        c.rows = rows;
+        c.row_stride = row_stride;
+        HIP_TRY(ro::launch_cut_windows(c, s));
+    }
     return RO_OK;
 }
 
@@ -802,7 +811,8 @@ extern "C" int ro_stft_set_bands(ro_stft_t *h, const ro_bands_t *bands)
 // when d_extra is given, plus the tile's log and its range when d_ln / d_minmax are
 static int run_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row, int64_t rows,
                         float *d_rows, int64_t row_stride, float *d_tile, ro_scan_record_t *d_records,
-                        ro_scan_record_t *d_extra, void *stream, float *d_ln = nullptr, float *d_minmax = nullptr)
+                        ro_scan_record_t *d_extra, void *stream, float *d_ln = nullptr, float *d_minmax = nullptr,
+                        const ro::CutArgs *cut = nullptr)
 {
     int rc = validate_resident(h, d_iq, format, samples, first_row, rows, d_rows, row_stride, d_tile,
                                d_records);
@@ -815,7 +825,7 @@ static int run_resident(ro_stft_t *h, const void *d_iq, int format, int64_t samp
     // (the fused epilogue always writes the log when asked for its range: the partial min / max come with it)
     rc = launch_transform(h, d_iq, format, first_row, rows, d_rows, row_stride, s, d_tile, d_records, d_ln);
     if (rc != RO_OK) return rc;
-    rc = launch_tile_and_scan(h, d_rows, row_stride, rows, d_tile, d_records, s, d_ln, d_minmax, d_extra);
+    rc = launch_tile_and_scan(h, d_rows, row_stride, rows, d_tile, d_records, s, d_ln, d_minmax, d_extra, cut);
     if (rc != RO_OK) return rc;
     h->stat_launches += 1;
     h->stat_rows += rows;
@@ -905,6 +915,55 @@ extern "C" int ro_stft_scan_sets_resident(ro_stft_t *h, const float *d_rows, int
     if (d_records) HIP_TRY(ro::launch_scan(make_scan_args(h, d_rows, row_stride, rows, d_records), s));
     HIP_TRY(ro::launch_scan_sets(make_scan_sets_args(h, d_rows, row_stride, rows, d_extra), s));
     return RO_OK;
+}
+
+// ---------------------------------------------------------------------------
+// tile windows: several recorders' column cuts of full rows (src/WaterfallBackend.cpp:174-205, :368-374) as one image
+// ---------------------------------------------------------------------------
+// what both calls ask of the window list and the image; *cut is ready for launch_tile_and_scan
+static int check_cut(const char *who, const ro_stft_t *h, const ro_band_window_t *w, int count, const float *d_image,
+                     int64_t image_stride, ro::CutArgs *cut)
+{
+    if (!h) return fail(RO_ERR_INVALID, "%s: null handle", who);
+    if (!w || !d_image) return fail(RO_ERR_INVALID, "%s: null %s", who, !w ? "windows" : "d_image");
+    int64_t total = 0;
+    const int rc = tile_windows_check(who, h->bins, w, count, &total);
+    if (rc != RO_OK) return rc;
+    if (image_stride < total)
+        return fail(RO_ERR_INVALID, "%s: image_stride %lld < the windows' %lld columns", who, (long long)image_stride,
+                    (long long)total);
+    *cut = make_cut_args(w, count, const_cast<float *>(d_image), image_stride);
+    return RO_OK;
+}
+
+extern "C" int ro_stft_cut_windows_resident(ro_stft_t *h, const float *d_rows, int64_t row_stride, int64_t rows,
+                                            const ro_band_window_t *w, int count, float *d_image, int64_t image_stride,
+                                            void *stream)
+{
+    ro::CutArgs cut{};
+    const int rc = check_cut("ro_stft_cut_windows_resident", h, w, count, d_image, image_stride, &cut);
+    if (rc != RO_OK) return rc;
+    if (!d_rows) return fail(RO_ERR_INVALID, "ro_stft_cut_windows_resident: null d_rows");
+    if (rows < 0 || row_stride < h->bins) return fail(RO_ERR_INVALID, "bad rows / row_stride");
+    if (rows == 0) return RO_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    cut.rows_in = d_rows;
+    cut.rows = rows;
+    cut.row_stride = row_stride;
+    HIP_TRY(ro::launch_cut_windows(cut, (hipStream_t)stream));
+    return RO_OK;
+}
+
+extern "C" int ro_stft_run_resident_windows(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
+                                            int64_t rows, float *d_rows, int64_t row_stride, const ro_band_window_t *w,
+                                            int count, float *d_image, int64_t image_stride, ro_scan_record_t *d_records,
+                                            ro_scan_record_t *d_extra, void *stream)
+{
+    ro::CutArgs cut{};
+    const int rc = check_cut("ro_stft_run_resident_windows", h, w, count, d_image, image_stride, &cut);
+    if (rc != RO_OK) return rc;
+    return run_resident(h, d_iq, format, samples, first_row, rows, d_rows, row_stride, nullptr, d_records, d_extra, stream,
+                        nullptr, nullptr, &cut);
 }
 
 extern "C" int ro_stft_extra_bands(const ro_stft_t *h, ro_bands_t *sets_out)

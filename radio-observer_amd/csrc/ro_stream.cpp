@@ -69,6 +69,8 @@ int ensure_stream_slots(ro_stft *h)
             ok(sl.d_tile.alloc((size_t)h->batch_rows * h->cfg.tile_cols));
         if (h->extra_count > 0)
             ok(sl.d_extra.alloc((size_t)h->batch_rows * h->extra_count));
+        if (h->tile_win_count > 0)
+            ok(sl.d_image.alloc((size_t)h->batch_rows * h->tile_win_total));
         if (h->cfg.tile_ln)
             ok(sl.d_ln.alloc((size_t)h->batch_rows * h->cfg.tile_cols)) && ok(sl.d_minmax.alloc((size_t)h->batch_rows * 2));
     }
@@ -246,15 +248,19 @@ int run_stream_batch(ro_stft *h, int64_t rows)
         step(hipEventRecord(b->k0, h->stream), "hipEventRecord");
     if (rc == RO_OK) {
         ro_scan_record_t *recs = h->cfg.enable_scan ? sl.d_records : nullptr;
+        // (tile windows: the image is cut behind the rows, compact; such a handle has neither a tile nor a sink)
+        const ro::CutArgs cut = make_cut_args(h->tile_win, h->tile_win_count, sl.d_image, h->tile_win_total);
         rc = launch_transform(h, sl.d_iq, h->stage_fmt, 0, rows, sl.d_rows, h->bins, h->stream, sl.d_tile, recs, sl.d_ln);
         if (rc == RO_OK)
-            rc = launch_tile_and_scan(h, sl.d_rows, h->bins, rows, sl.d_tile, recs, h->stream, sl.d_ln, sl.d_minmax, g_ext);
+            rc = launch_tile_and_scan(h, sl.d_rows, h->bins, rows, sl.d_tile, recs, h->stream, sl.d_ln, sl.d_minmax, g_ext,
+                                      h->tile_win_count > 0 ? &cut : nullptr);
     }
     step(hipEventRecord(b->k1, h->stream), "hipEventRecord") && step(hipEventRecord(sl.computed, h->stream), "hipEventRecord");
-    // download (s_out): only the columns somebody asked for travel -- the tile when one is configured
+    // download (s_out): only the columns somebody asked for travel -- the tile when one is configured, the tile windows'
+    // image when they are set
     step(hipStreamWaitEvent(h->s_out, sl.computed, 0), "hipStreamWaitEvent");
     if (rc == RO_OK) {
-        const float *src = h->cfg.tile_cols > 0 ? sl.d_tile : sl.d_rows;
+        const float *src = h->tile_win_count > 0 ? sl.d_image : h->cfg.tile_cols > 0 ? sl.d_tile : sl.d_rows;
         if (h->sink) {
             // straight into the caller's ring: row r of the stream at slot (sink_first + r) mod sink_cap, in at most
             // two runs of consecutive slots
@@ -506,7 +512,7 @@ static int fetch_rows(ro_stft_t *h, int64_t max_rows, int first_col, int cols, f
     if (rows_out && (first_col < h->out_first || cols <= 0 || first_col + cols > h->out_first + h->out_cols))
         return fail(RO_ERR_INVALID, "columns [%d,+%d) outside [%d,+%d) -- what this handle brings to the host%s",
                     first_col, cols, h->out_first, h->out_cols,
-                    h->cfg.tile_cols > 0 ? " (the configured tile)" : "");
+                    h->tile_win_count > 0 ? " (image columns of its tile windows)" : h->cfg.tile_cols > 0 ? " (the configured tile)" : "");
     if (records_out && !h->cfg.enable_scan) return fail(RO_ERR_STATE, "scan records requested but scan is off");
     if (rows_out && h->sink) return fail(RO_ERR_STATE, "this handle's rows go to its row sink (ro_stft_set_row_sink): pass rows_out = NULL");
     const double t0 = now_ms();
@@ -595,6 +601,56 @@ extern "C" int ro_stft_set_extra_bands(ro_stft_t *h, const ro_bands_t *sets, int
     return RO_OK;
 }
 
+// The tile windows of a handle's streaming path (several recorders' column cuts, src/WaterfallBackend.cpp:174-205,
+// :368-374).  Everything sized by their total starts over: the slots' image blocks and the pinned batches.  (No captured
+// graph holds them: graphs need a row sink, and a sink and windows refuse each other.)
+extern "C" int ro_stft_set_tile_windows(ro_stft_t *h, const ro_band_window_t *windows, int count)
+{
+    if (!h) return fail(RO_ERR_INVALID, "null handle");
+    if (h->cfg.tile_cols > 0 || h->cfg.tile_ln)
+        return fail(RO_ERR_UNSUPPORTED, "tile windows are for handles created without a tile (tile_cols = %d, tile_ln = %d)",
+                    h->cfg.tile_cols, h->cfg.tile_ln);
+    int64_t total = 0;
+    if (count != 0) {
+        const int rc = tile_windows_check("ro_stft_set_tile_windows", h->bins, windows, count, &total);
+        if (rc != RO_OK) return rc;
+    }
+    if (h->sink) return fail(RO_ERR_STATE, "this handle's rows go to its row sink (ro_stft_set_row_sink): remove it first");
+    if (!h->ready.empty() || h->staged_have > 0)
+        return fail(RO_ERR_STATE, "the tile windows can only change on an idle stream (after create or ro_stft_reset)");
+    HIP_TRY(hipSetDevice(h->device));
+    // nothing of the handle's may still be running on the old blocks
+    if (h->s_in) HIP_TRY(hipStreamSynchronize(h->s_in));
+    if (h->stream) HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->s_out) HIP_TRY(hipStreamSynchronize(h->s_out));
+    for (auto &sl : h->slot) {
+        if (sl.gstream) HIP_TRY(hipStreamSynchronize(sl.gstream));
+        sl.d_image.reset();
+    }
+    while (!h->batch_pool.empty()) { destroy_batch(h->batch_pool.back()); h->batch_pool.pop_back(); }
+    h->tile_win_count = 0;
+    h->tile_win_total = 0;
+    h->out_first = 0;                         // full rows again (the handle has no tile)
+    h->out_cols = h->bins;
+    if (count == 0) return RO_OK;
+    if (h->slots_ready)                       // (else the first push allocates them with the other streaming buffers)
+        for (auto &sl : h->slot)
+            HIP_TRY(sl.d_image.alloc((size_t)h->batch_rows * (size_t)total));
+    for (int i = 0; i < count; ++i) h->tile_win[i] = windows[i];
+    h->tile_win_count = count;
+    h->tile_win_total = (int)total;
+    h->out_cols = (int)total;
+    return RO_OK;
+}
+
+extern "C" int ro_stft_tile_windows(const ro_stft_t *h, ro_band_window_t *out)
+{
+    if (!h) return fail(RO_ERR_INVALID, "null handle");
+    if (out)
+        for (int i = 0; i < h->tile_win_count; ++i) out[i] = h->tile_win[i];
+    return h->tile_win_count;
+}
+
 // rows at the head of the output queue whose batches have FINISHED (download included): what ro_stft_fetch hands over
 // without waiting.  A caller that fetches only these keeps the next batch's upload and kernels in flight under the
 // previous batch's download and under its own per-row work, instead of waiting out every batch it has just launched.
@@ -660,6 +716,9 @@ extern "C" int ro_stft_set_row_sink(ro_stft_t *h, float *base, int64_t row_strid
     if (!h->ready.empty() || h->staged_have > 0)
         return fail(RO_ERR_STATE, "the row sink can only change on an idle stream (after create or ro_stft_reset)");
     if (h->cfg.tile_ln) return fail(RO_ERR_UNSUPPORTED, "a tile_ln handle hands its rows out through ro_stft_fetch_ln");
+    if (h->tile_win_count > 0)
+        return fail(RO_ERR_STATE, "a handle with tile windows hands its image out through ro_stft_fetch: remove the windows first "
+                                  "(ro_stft_set_tile_windows with count = 0)");
     HIP_TRY(hipSetDevice(h->device));
     // (batches made with a sink hold no row buffer, batches made without one do: the pool starts over either way)
     while (!h->batch_pool.empty()) { destroy_batch(h->batch_pool.back()); h->batch_pool.pop_back(); }
