@@ -444,6 +444,89 @@ int ro_stft_run_resident_windows(ro_stft_t *h, const void *d_iq, int format, int
                                  float *d_image, int64_t image_stride,
                                  ro_scan_record_t *d_records, ro_scan_record_t *d_extra, void *stream);
 
+/* ---- the detector: events from scan records ------------------------------------
+ * What BolidRecorder::update does with a row's record once noise(), peak() and average() are known: the decision
+ * (src/BolidRecorder.cpp:135) and the three-state machine behind it (:171-267).  With mark = row + 1 (buffer_->mark(),
+ * unwrapped) the machine has a closed form:
+ *   detect(r) = (double)average > (double)noise * 2.0 (:135; false for a NaN), G = max(2, jitter) (:196-201: duration_
+ *   counts from 1 at the first quiet row and is compared AFTER its increment, so a burst never ends sooner than two rows
+ *   behind its last detect row).  Detect rows whose gaps are at most G - 1 quiet rows form one GROUP (STATE_BOLID <->
+ *   STATE_BOLID_ENDED, :185-200).  A group with first detect row r0 and last detect row `last` FIRES at row last + G
+ *   (:201-264), with  start_row = r0 + 1 - advance  (nextSnapshot_.start = mark - advance_, :178; may be negative),
+ *   length = 2 advance + (last - r0 + 1)  (:179, :189: the quiet rows inside the group count, :196), and noise, peak,
+ *   magnitude = the record of row r0 (:174-176; peak is the column, peakFreq_ = binToFrequency(low_detect + peak)).
+ * A group whose fire row has not been seen yet is the carried state. */
+typedef struct ro_detector {
+    int32_t advance;               /* advance_ in rows (src/BolidRecorder.cpp:100), >= 0 */
+    int32_t jitter;                /* jitter_ in rows (:101), >= 0                        */
+} ro_detector_t;
+
+typedef struct ro_event {          /* 40 bytes: the METEOR DETECTED branch, src/BolidRecorder.cpp:201-264 */
+    int64_t fire_row;              /* the row whose update() fired                        */
+    int64_t start_row;             /* nextSnapshot_.start, :178                           */
+    int64_t length;                /* nextSnapshot_.length, :179, :189                    */
+    float   noise;                 /* noise_, :175                                        */
+    int32_t peak;                  /* the peak column behind peakFreq_, :174              */
+    float   magnitude;             /* magnitude_, :176                                    */
+    int32_t reserved;              /* 0                                                   */
+} ro_event_t;
+
+typedef struct ro_detect_state {   /* 32 bytes; all zero = STATE_INIT (:108), and every state that is not open is all zero */
+    int64_t first_detect_row;      /* r0 of the open group                                */
+    int64_t last_detect_row;       /* its last detect row so far                          */
+    float   noise;                 /* the record of row r0 (:174-176)                     */
+    int32_t peak;
+    float   magnitude;
+    int32_t open;                  /* 1: STATE_BOLID or STATE_BOLID_ENDED                 */
+} ro_detect_state_t;
+
+typedef struct ro_detect_summary { /* 24 bytes, per call */
+    int64_t events;                /* events fired in the call, also those beyond `capacity` */
+    int64_t detect_rows;           /* rows with detect(r)                                 */
+    int64_t marginal_rows;         /* rows with fabs((double)a / (2.0 * (double)n) - 1.0) <= 1e-5: a decision that a last
+                                    * bit of the transform could turn (SURVEY 7's per-mode figure) */
+} ro_detect_summary_t;
+
+/* The machine on the host, for ONE set: records[i * record_stride] is the record of row first_row + i (record_stride 1
+ * for a primary's array, 1 + ... for a column of a [row][set] array such as ro_stft_fetch_sets hands out), rows >= 0.
+ * state: in / out, zero-filled by the caller once.  An open state whose group could no longer fire (last_detect_row + G <
+ * first_row: rows were left out) is closed silently.  events (capacity entries, NULL with capacity = 0): filled in
+ * ascending fire_row; events beyond capacity are counted in summary->events and not written.  summary and detect (rows
+ * bytes of 0 / 1) may be NULL.  rows == 0 changes nothing but *summary, which becomes zeros.  RO_ERR_INVALID for null
+ * records (rows > 0), det or state, record_stride < 1, a negative advance, jitter, rows or capacity, and events == NULL
+ * with capacity > 0.  Pure host, no device. */
+int ro_events_host(const ro_scan_record_t *records, int64_t record_stride, int64_t first_row, int64_t rows,
+                   const ro_detector_t *det, ro_detect_state_t *state, ro_event_t *events, int64_t capacity,
+                   ro_detect_summary_t *summary, uint8_t *detect);
+
+/* The same machine on the device for every set of the handle at once (csrc/ro_events.hip: a scan, three plain launches per
+ * RO_EVENTS_CHUNK_ROWS rows), bit for bit what ro_events_host gives per set.  SLOT 0 is the primary (d_records, rows
+ * records), slots 1 + s the handle's extra sets (d_extra[r * count + s], as ro_stft_run_resident_sets writes them).  Either
+ * pointer may be NULL, not both; a NULL pointer's slots are left untouched in every output.
+ *   detectors   host, 1 + count entries
+ *   d_state     device, 1 + count entries, in / out; zero-filled by the caller once
+ *   d_events    device, [slot][capacity], ascending fire_row; NULL with capacity = 0
+ *   d_summary   device, 1 + count entries, overwritten by every call; may be NULL
+ *   d_detect    device, [row][1 + count] bytes of 0 / 1; may be NULL
+ * rows == 0 is RO_OK and changes nothing but the summaries, which become zeros.  RO_ERR_INVALID for a null handle or
+ * state, both record pointers null, a negative rows or capacity, d_events == NULL with capacity > 0, a negative advance or
+ * jitter (the message names the set); RO_ERR_STATE for d_extra on a handle without extra sets.  Asynchronous on `stream`;
+ * uses handle scratch (the tiles' totals), so one launch of a handle in flight at a time unless they share a stream. */
+int ro_stft_events_resident(ro_stft_t *h, const ro_scan_record_t *d_records, const ro_scan_record_t *d_extra,
+                            int64_t first_row, int64_t rows, const ro_detector_t *detectors,
+                            ro_detect_state_t *d_state, ro_event_t *d_events, int64_t capacity,
+                            ro_detect_summary_t *d_summary, uint8_t *d_detect, void *stream);
+
+/* ro_stft_run_resident_sets, then ro_stft_events_resident on the records it has just written, on the same stream: from
+ * samples to events nothing waits for the host (src/FFTBackend.cpp:211-257 through src/BolidRecorder.cpp:119-267).  The
+ * rows and records are the bits ro_stft_run_resident_sets gives; d_records, d_extra or both.  Every refusal of either call
+ * is made before anything is launched. */
+int ro_stft_run_resident_events(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row, int64_t rows,
+                                float *d_rows, int64_t row_stride, float *d_tile,
+                                ro_scan_record_t *d_records, ro_scan_record_t *d_extra,
+                                const ro_detector_t *detectors, ro_detect_state_t *d_state, ro_event_t *d_events,
+                                int64_t capacity, ro_detect_summary_t *d_summary, uint8_t *d_detect, void *stream);
+
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel
  * when records are requested).  kernel_ms_out (optional, 2 floats) receives the

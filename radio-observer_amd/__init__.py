@@ -17,7 +17,8 @@ from .capi import (  # noqa: F401
     clamp_overlap, fft_sample_rate, frequency_to_bin, bin_to_frequency, time_to_fft_samples,
     row_count, window_table, bins_supported, device_count, shard_rows, shard_samples, shard_max_rows,
     stitch_rows, ln_levels, band_supported, bands_hull, band_windows_supported, bands_windows,
-    tile_windows_supported, merge_windows,
+    tile_windows_supported, merge_windows, events_host, Detector,
+    EVENT_DTYPE, DETECT_STATE_DTYPE, DETECT_SUMMARY_DTYPE,
     RO_WINDOW_NUTTALL, RO_WINDOW_HANN, RO_WINDOW_CUSTOM, RO_IQ_F32, RO_IQ_I16, RO_IQ_F64,
     RO_PRECISION_F32, RO_PRECISION_F64,
 )

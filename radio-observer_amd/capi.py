@@ -62,6 +62,19 @@ class Timing(C.Structure):
 SCAN_DTYPE = np.dtype([("noise", np.float32), ("peak", np.int32), ("average", np.float32)])
 
 
+class Detector(C.Structure):
+    """ro_detector_t -- advance_ and jitter_ of a BolidRecorder, in rows (src/BolidRecorder.cpp:100-101)."""
+    _fields_ = [("advance", C.c_int32), ("jitter", C.c_int32)]
+
+
+# ro_event_t (40 bytes), ro_detect_state_t (32, all zero = STATE_INIT), ro_detect_summary_t (24)
+EVENT_DTYPE = np.dtype([("fire_row", np.int64), ("start_row", np.int64), ("length", np.int64), ("noise", np.float32),
+                        ("peak", np.int32), ("magnitude", np.float32), ("reserved", np.int32)])
+DETECT_STATE_DTYPE = np.dtype([("first_detect_row", np.int64), ("last_detect_row", np.int64), ("noise", np.float32),
+                               ("peak", np.int32), ("magnitude", np.float32), ("open", np.int32)])
+DETECT_SUMMARY_DTYPE = np.dtype([("events", np.int64), ("detect_rows", np.int64), ("marginal_rows", np.int64)])
+
+
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bins", C.c_int32), ("overlap", C.c_int32),
                 ("sample_rate", C.c_int32), ("window_kind", C.c_int32),
@@ -150,6 +163,13 @@ _EXPORTS = {
                                                C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ro_stft_set_tile_windows": (C.c_int, [C.c_void_p, C.POINTER(BandWindow), C.c_int]),
     "ro_stft_tile_windows": (C.c_int, [C.c_void_p, C.POINTER(BandWindow)]),
+    "ro_events_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(Detector), C.c_void_p, C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_void_p]),
+    "ro_stft_events_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(Detector),
+                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ro_stft_run_resident_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Detector),
+                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -388,6 +408,41 @@ def merge_windows(ranges, bins):
     return [BandWindow(out[i].first_col, out[i].cols) for i in range(count.value)], [int(offs[i]) for i in range(n)]
 
 
+def _detectors(detectors):
+    """Detector or (advance, jitter) each -> ctypes array"""
+    arr = (Detector * max(len(detectors), 1))()
+    for i, d in enumerate(detectors):
+        arr[i] = d if isinstance(d, Detector) else Detector(*d)
+    return arr
+
+
+def events_host(records, detector, first_row=0, state=None, capacity=None, want_detect=False):
+    """BolidRecorder::update's decision and state machine over one set's records (a 1-D SCAN_DTYPE array, any stride: a
+    column of a [row][set] array will do) -- ro_events_host.  detector: Detector or (advance, jitter).  state: a
+    DETECT_STATE_DTYPE array of one entry, updated in place (None: a fresh one).  capacity: events kept (None: all).
+    Returns (events, state, summary, detect): EVENT_DTYPE array of the events written, the state, a DETECT_SUMMARY_DTYPE
+    scalar and the per-row decisions (uint8, or None)."""
+    records = np.asarray(records)
+    if records.dtype != SCAN_DTYPE or records.ndim != 1:
+        raise ValueError("records: a one-dimensional SCAN_DTYPE array")
+    rows = records.shape[0]
+    stride = records.strides[0] // SCAN_DTYPE.itemsize if rows else 1
+    if rows and (records.strides[0] % SCAN_DTYPE.itemsize or stride < 1):
+        raise ValueError("records: a stride of whole records, ascending")
+    if state is None:
+        state = np.zeros(1, DETECT_STATE_DTYPE)
+    cap = rows if capacity is None else capacity
+    events = np.zeros(max(cap, 0), EVENT_DTYPE)
+    summary = np.zeros(1, DETECT_SUMMARY_DTYPE)
+    detect = np.zeros(rows, np.uint8) if want_detect else None
+    det = _detectors([detector])
+    _check(library().ro_events_host(C.c_void_p(records.ctypes.data) if rows else None, stride, first_row, rows, det,
+                                    C.c_void_p(state.ctypes.data), C.c_void_p(events.ctypes.data) if cap > 0 else None,
+                                    cap, C.c_void_p(summary.ctypes.data),
+                                    C.c_void_p(detect.ctypes.data) if detect is not None and rows else None))
+    return events[:min(int(summary["events"][0]), max(cap, 0))], state, summary[0], detect
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -508,6 +563,30 @@ class Stft:
         _check(library().ro_stft_run_resident_sets(self._h, _ptr(d_iq), fmt, samples, first_row, rows,
                                                    _ptr(d_rows), row_stride or self.bins, _ptr(d_tile),
                                                    _ptr(d_records), _ptr(d_extra), _ptr(stream)))
+
+    def events_resident(self, rows, detectors, d_state, d_records=None, d_extra=None, first_row=0, d_events=None,
+                        capacity=0, d_summary=None, d_detect=None, stream=None):
+        """events from scan records that are in HBM, for the primary (d_records: slot 0) and the extra sets (d_extra: slots
+        1 + s) at once -- ro_stft_events_resident.  detectors: 1 + extra_count of Detector or (advance, jitter); d_state:
+        1 + extra_count DETECT_STATE_DTYPE entries, zero-filled once; d_events: [slot][capacity] EVENT_DTYPE; d_summary:
+        1 + extra_count DETECT_SUMMARY_DTYPE; d_detect: [row][1 + extra_count] bytes"""
+        if len(detectors) != 1 + self.extra_count:
+            raise ValueError("detectors: one per slot, %d" % (1 + self.extra_count))
+        _check(library().ro_stft_events_resident(self._h, _ptr(d_records), _ptr(d_extra), first_row, rows,
+                                                 _detectors(detectors), _ptr(d_state), _ptr(d_events), capacity,
+                                                 _ptr(d_summary), _ptr(d_detect), _ptr(stream)))
+
+    def run_resident_events(self, d_iq, fmt, samples, first_row, rows, d_rows, detectors, d_state, row_stride=None,
+                            d_tile=None, d_records=None, d_extra=None, d_events=None, capacity=0, d_summary=None,
+                            d_detect=None, stream=None):
+        """run_resident_sets, then events_resident on the records it has just written, on the same stream: samples in,
+        events out -- ro_stft_run_resident_events"""
+        if len(detectors) != 1 + self.extra_count:
+            raise ValueError("detectors: one per slot, %d" % (1 + self.extra_count))
+        _check(library().ro_stft_run_resident_events(self._h, _ptr(d_iq), fmt, samples, first_row, rows, _ptr(d_rows),
+                                                     row_stride or self.bins, _ptr(d_tile), _ptr(d_records),
+                                                     _ptr(d_extra), _detectors(detectors), _ptr(d_state), _ptr(d_events),
+                                                     capacity, _ptr(d_summary), _ptr(d_detect), _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

@@ -277,6 +277,74 @@ extern "C" int ro_merge_windows(const ro_band_window_t *ranges, int range_count,
     return RO_OK;
 }
 
+// ---------------------------------------------------------------------------
+// the detector on the host: BolidRecorder::update's decision and state machine (src/BolidRecorder.cpp:135, :171-267) in
+// the closed form of include/ro_stft.h, one row at a time.  ro_events.hip computes the same as a scan.
+// ---------------------------------------------------------------------------
+static_assert(sizeof(ro_detector_t) == 8 && sizeof(ro_event_t) == 40 && sizeof(ro_detect_state_t) == 32 &&
+                  sizeof(ro_detect_summary_t) == 24, "the detector's structs are ABI");
+
+extern "C" int ro_events_host(const ro_scan_record_t *records, int64_t record_stride, int64_t first_row, int64_t rows,
+                              const ro_detector_t *det, ro_detect_state_t *state, ro_event_t *events, int64_t capacity,
+                              ro_detect_summary_t *summary, uint8_t *detect)
+{
+    if (!det || !state) return fail(RO_ERR_INVALID, "ro_events_host: null %s", !det ? "detector" : "state");
+    if (det->advance < 0 || det->jitter < 0)
+        return fail(RO_ERR_INVALID, "ro_events_host: advance %d, jitter %d: neither may be negative", det->advance, det->jitter);
+    if (rows < 0 || capacity < 0)
+        return fail(RO_ERR_INVALID, "ro_events_host: rows %lld, capacity %lld: neither may be negative", (long long)rows,
+                    (long long)capacity);
+    if (capacity > 0 && !events) return fail(RO_ERR_INVALID, "ro_events_host: null events with capacity %lld", (long long)capacity);
+    if (rows > 0 && (!records || record_stride < 1))
+        return fail(RO_ERR_INVALID, "ro_events_host: %s", !records ? "null records" : "record_stride < 1");
+    ro_detect_summary_t sum{};
+    if (rows == 0) {
+        if (summary) *summary = sum;
+        return RO_OK;
+    }
+    const int64_t G = det->jitter > 2 ? det->jitter : 2;
+    ro_detect_state_t st = *state;
+    // a group that could no longer fire (rows were left out between two calls) is closed silently
+    if (st.open && st.last_detect_row + G < first_row) st.open = 0;
+    for (int64_t i = 0; i < rows; ++i) {
+        const ro_scan_record_t &rec = records[i * record_stride];
+        const int64_t r = first_row + i;
+        const double n = (double)rec.noise, a = (double)rec.average;
+        const bool d = a > n * 2.0;                                     // :135
+        if (std::fabs(a / (2.0 * n) - 1.0) <= 1e-5) sum.marginal_rows += 1;
+        if (detect) detect[i] = d ? 1 : 0;
+        if (d) {
+            sum.detect_rows += 1;
+            if (!st.open) {                                             // STATE_INIT -> STATE_BOLID, :173-182
+                st.open = 1;
+                st.first_detect_row = r;
+                st.noise = rec.noise;
+                st.peak = rec.peak;
+                st.magnitude = rec.average;
+            }
+            st.last_detect_row = r;                                     // STATE_BOLID, or back to it (:186-187, :198-199)
+        } else if (st.open && r == st.last_detect_row + G) {            // duration_ >= jitter_, :201-264
+            if (sum.events < capacity) {
+                ro_event_t &e = events[sum.events];
+                e.fire_row = r;
+                e.start_row = st.first_detect_row + 1 - det->advance;
+                e.length = 2 * (int64_t)det->advance + (st.last_detect_row - st.first_detect_row + 1);
+                e.noise = st.noise;
+                e.peak = st.peak;
+                e.magnitude = st.magnitude;
+                e.reserved = 0;
+            }
+            sum.events += 1;
+            st.open = 0;
+        }
+    }
+    if (!st.open) st = ro_detect_state_t{};                             // every state that is not open is all zero
+    else st.open = 1;
+    *state = st;
+    if (summary) *summary = sum;
+    return RO_OK;
+}
+
 extern "C" int ro_ln_levels(const float *ln, int64_t count, float mn, float mx, uint8_t *levels_out)
 {
     if (count < 0 || (count > 0 && (!ln || !levels_out))) return fail(RO_ERR_INVALID, "ro_ln_levels: bad arguments");

@@ -31,6 +31,7 @@
 #include "ro_band.h"
 #include "ro_band_f64.h"
 #include "ro_band_windows.h"
+#include "ro_events.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -247,6 +248,11 @@ struct ro_stft {
     // tile_ln: partial min / max of the fused epilogue's two tile waves (rows x 4 floats), grown on demand
     DeviceBlock<float> d_ln_part;
     int64_t ln_part_rows = 0;
+
+    // the detector (ro_stft_events_resident): heads, tile totals and tile prefixes of one chunk (ro_events.h), allocated at
+    // their full size (ro::EVENTS_SCRATCH_BYTES, under 0.5 MiB) by the first call -- the block never grows, so no launch
+    // ever has to be waited for
+    DeviceBlock<char> d_events_scratch;
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
     // belong to (one window for the consecutive call; empty: none); a handle has one precision, so one of the two sets is

@@ -966,6 +966,89 @@ extern "C" int ro_stft_run_resident_windows(ro_stft_t *h, const void *d_iq, int 
                         nullptr, nullptr, &cut);
 }
 
+// ---------------------------------------------------------------------------
+// the detector on the device: events from scan records (src/BolidRecorder.cpp:135, :171-267; ro_events.hip)
+// ---------------------------------------------------------------------------
+// what both calls ask of the detector's arguments
+static int check_events(const char *who, const ro_stft_t *h, const ro_scan_record_t *d_records, const ro_scan_record_t *d_extra,
+                        int64_t rows, const ro_detector_t *detectors, const ro_detect_state_t *d_state,
+                        const ro_event_t *d_events, int64_t capacity)
+{
+    if (!h) return fail(RO_ERR_INVALID, "%s: null handle", who);
+    if (!d_state || !detectors) return fail(RO_ERR_INVALID, "%s: null %s", who, !d_state ? "d_state" : "detectors");
+    if (!d_records && !d_extra) return fail(RO_ERR_INVALID, "%s: null d_records and null d_extra: one of them is needed", who);
+    if (rows < 0 || capacity < 0)
+        return fail(RO_ERR_INVALID, "%s: rows %lld, capacity %lld: neither may be negative", who, (long long)rows,
+                    (long long)capacity);
+    if (capacity > 0 && !d_events) return fail(RO_ERR_INVALID, "%s: null d_events with capacity %lld", who, (long long)capacity);
+    if (d_extra && h->extra_count == 0)
+        return fail(RO_ERR_STATE, "%s: d_extra, but no extra band sets are set (ro_stft_set_extra_bands)", who);
+    for (int i = 0; i <= h->extra_count; ++i)
+        if (detectors[i].advance < 0 || detectors[i].jitter < 0)
+            return fail(RO_ERR_INVALID, "%s: set %d: advance %d, jitter %d: neither may be negative", who, i,
+                        detectors[i].advance, detectors[i].jitter);
+    return RO_OK;
+}
+
+// the launches (check_events has passed): chunks of RO_EVENTS_CHUNK_ROWS rows chained through d_state on the stream
+static int launch_events_chunks(ro_stft_t *h, const ro_scan_record_t *d_records, const ro_scan_record_t *d_extra,
+                                int64_t first_row, int64_t rows, const ro_detector_t *detectors, ro_detect_state_t *d_state,
+                                ro_event_t *d_events, int64_t capacity, ro_detect_summary_t *d_summary, uint8_t *d_detect,
+                                hipStream_t s)
+{
+    const int count = h->extra_count;
+    if (rows == 0) {                             // nothing changes but the summaries of the slots asked for
+        if (d_summary && d_records) HIP_TRY(hipMemsetAsync(d_summary, 0, sizeof(ro_detect_summary_t), s));
+        if (d_summary && d_extra) HIP_TRY(hipMemsetAsync(d_summary + 1, 0, (size_t)count * sizeof(ro_detect_summary_t), s));
+        return RO_OK;
+    }
+    if (!h->d_events_scratch) HIP_TRY(h->d_events_scratch.alloc(ro::EVENTS_SCRATCH_BYTES));
+    ro::EventsArgs a{};
+    ro::events_scratch_layout(a, h->d_events_scratch);
+    a.count = count;
+    a.state = d_state;
+    a.events = d_events;
+    a.capacity = capacity;
+    a.summary = d_summary;
+    for (int i = 0; i <= count; ++i) a.det[i] = detectors[i];
+    for (int64_t done = 0; done < rows; done += RO_EVENTS_CHUNK_ROWS) {
+        a.primary = d_records ? d_records + done : nullptr;
+        a.extra = d_extra ? d_extra + done * count : nullptr;
+        a.accumulate = done > 0;
+        a.first_row = first_row + done;
+        a.rows = std::min<int64_t>(RO_EVENTS_CHUNK_ROWS, rows - done);
+        a.detect = d_detect ? d_detect + done * (1 + count) : nullptr;
+        HIP_TRY(ro::launch_events(a, s));
+    }
+    return RO_OK;
+}
+
+extern "C" int ro_stft_events_resident(ro_stft_t *h, const ro_scan_record_t *d_records, const ro_scan_record_t *d_extra,
+                                       int64_t first_row, int64_t rows, const ro_detector_t *detectors,
+                                       ro_detect_state_t *d_state, ro_event_t *d_events, int64_t capacity,
+                                       ro_detect_summary_t *d_summary, uint8_t *d_detect, void *stream)
+{
+    const int rc = check_events("ro_stft_events_resident", h, d_records, d_extra, rows, detectors, d_state, d_events, capacity);
+    if (rc != RO_OK) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    return launch_events_chunks(h, d_records, d_extra, first_row, rows, detectors, d_state, d_events, capacity, d_summary,
+                                d_detect, (hipStream_t)stream);
+}
+
+extern "C" int ro_stft_run_resident_events(ro_stft_t *h, const void *d_iq, int format, int64_t samples, int64_t first_row,
+                                           int64_t rows, float *d_rows, int64_t row_stride, float *d_tile,
+                                           ro_scan_record_t *d_records, ro_scan_record_t *d_extra,
+                                           const ro_detector_t *detectors, ro_detect_state_t *d_state, ro_event_t *d_events,
+                                           int64_t capacity, ro_detect_summary_t *d_summary, uint8_t *d_detect, void *stream)
+{
+    int rc = check_events("ro_stft_run_resident_events", h, d_records, d_extra, rows, detectors, d_state, d_events, capacity);
+    if (rc != RO_OK) return rc;
+    rc = run_resident(h, d_iq, format, samples, first_row, rows, d_rows, row_stride, d_tile, d_records, d_extra, stream);
+    if (rc != RO_OK) return rc;
+    return launch_events_chunks(h, d_records, d_extra, first_row, rows, detectors, d_state, d_events, capacity, d_summary,
+                                d_detect, (hipStream_t)stream);
+}
+
 extern "C" int ro_stft_extra_bands(const ro_stft_t *h, ro_bands_t *sets_out)
 {
     if (!h) return fail(RO_ERR_INVALID, "null handle");
