@@ -527,6 +527,106 @@ int ro_stft_run_resident_events(ro_stft_t *h, const void *d_iq, int format, int6
                                 const ro_detector_t *detectors, ro_detect_state_t *d_state, ro_event_t *d_events,
                                 int64_t capacity, ro_detect_summary_t *d_summary, uint8_t *d_detect, void *stream);
 
+/* ---- event snapshots: each event's rows, cut from a row ring ---------------------
+ * What the METEOR DETECTED branch ends in (src/BolidRecorder.cpp:262-263): startWriting() clamps the snapshot to
+ * snapshotRows_ and reserves rows [start, start + length) of the row ring (src/WaterfallBackend.cpp:107-127); the worker
+ * writes them once the ring holds them all (:60-104, :202-205).  A snapshot ends `advance` rows behind its group's last
+ * detect row, so at the fire row it is routinely still incomplete.  Here the ring lives in HBM (the reference's
+ * RingBuffer2D without its reservation: the caller sizes the ring instead), and one call per chunk reads the events where
+ * ro_stft_events_resident left them, carries the incomplete ones from call to call and packs the rows of every complete
+ * one into an arena with a directory.  The rows are opaque, `cols` floats each: the image of
+ * ro_stft_run_resident_windows or ro_stft_band_windows_resident, a tile, or full rows. */
+typedef struct ro_row_ring {       /* 32 bytes; the caller owns the memory */
+    float   *d_rows;               /* device: ring_rows x stride floats; stream row r >= 0 lives in slot r % ring_rows */
+    int64_t  stride;               /* floats between slots, >= cols; floats [cols, stride) of a slot are never touched */
+    int64_t  ring_rows;            /* >= 1 */
+    int32_t  cols;                 /* >= 1 */
+    int32_t  reserved;             /* 0 */
+} ro_row_ring_t;
+
+enum { RO_SNAP_CAPTURED = 0, RO_SNAP_EMPTY = 1, RO_SNAP_LOST = 2 };
+
+typedef struct ro_snapshot {       /* 72 bytes: one resolved event */
+    ro_event_t event;              /* as ro_stft_events_resident wrote it */
+    int64_t    first_row;          /* lo, below */
+    int64_t    offset;             /* floats into d_arena: rows x cols floats, row-major, stride cols; 0 unless CAPTURED */
+    int32_t    rows;               /* hi - lo if CAPTURED, else 0 */
+    int32_t    slot;
+    int32_t    status;             /* RO_SNAP_* */
+    int32_t    reserved;           /* 0 */
+} ro_snapshot_t;
+
+typedef struct ro_snap_summary {   /* 64 bytes, one per call, overwritten by every call */
+    int64_t resolved;              /* entries written to d_dir */
+    int64_t captured, empty, lost; /* of those, by status */
+    int64_t pending;               /* entries in the pending lists after the call, all slots of the mask */
+    int64_t pending_dropped;       /* candidates that found no room in a pending list: gone, counted here */
+    int64_t unlisted;              /* sum over the mask's slots of max(0, summary.events - capacity): fired but never written */
+    int64_t arena_floats;          /* floats of d_arena used */
+} ro_snap_summary_t;
+
+/* Rows into the ring: row i of d_image (rows x image_stride floats, image_stride >= cols) is stream row first_row + i, and
+ * its first `cols` floats go to slot (first_row + i) % ring_rows.  One launch; the wrap is computed in the kernel.  With
+ * rows > ring_rows only the last ring_rows rows are written, so that every slot is stored exactly once and two runs give
+ * the same bytes.  rows == 0 is RO_OK.  RO_ERR_INVALID for a null handle, ring, ring->d_rows or d_image, a negative
+ * first_row or rows, image_stride < cols, and a ring with ring_rows < 1, cols < 1, stride < cols or reserved != 0.
+ * Asynchronous on `stream`. */
+int ro_stft_ring_put_resident(ro_stft_t *h, const float *d_image, int64_t image_stride, int64_t first_row, int64_t rows,
+                              const ro_row_ring_t *ring, void *stream);
+
+/* The snapshots of one call.
+ *   d_events, capacity, d_summary   [slot][capacity] and [slot], exactly as ro_stft_events_resident leaves them; the number
+ *                    of events of a slot is read ON THE DEVICE: min(d_summary[slot].events, capacity).  d_summary may be
+ *                    NULL with capacity = 0 (no event is read, `unlisted` is 0)
+ *   slot_mask        bit s: slot s takes part; the other slots are not read and not written anywhere (ro_stft_events_resident
+ *                    leaves a NULL record pointer's slots untouched).  `slots` is the highest set bit plus one
+ *   snapshot_rows    host, `slots` entries, each >= 1 where the mask has its bit: snapshotRows_
+ *   ring, head_row   the caller states that stream rows [max(0, head_row - ring_rows), head_row) are in the ring: put
+ *                    earlier on the same stream
+ *   d_pending, d_pending_count   [slots][pending_capacity] events and [slots] counts, in / out, zero-filled by the caller
+ *                    once (a count outside [0, pending_capacity] is read as the nearer bound); d_pending may be NULL with
+ *                    pending_capacity = 0
+ *   d_dir            room for slots x (capacity + pending_capacity) entries, so the directory cannot overflow
+ *   d_arena          arena_floats floats; NULL with arena_floats = 0
+ *   d_snap_summary   one entry
+ * A slot's CANDIDATES are its pending list, in order, followed by this call's events, in order; slots in ascending order.
+ * For a candidate e of slot s:  len = min(e.length, snapshot_rows[s])  (src/WaterfallBackend.cpp:113-115: the first rows are
+ * kept),  lo = max(e.start_row, 0),  hi = e.start_row + len,  and, in this order:
+ *   1  hi > head_row                  still PENDING: not resolved
+ *   2  hi <= lo                       resolves as RO_SNAP_EMPTY
+ *   3  lo < head_row - ring_rows      resolves as RO_SNAP_LOST: rows have been overwritten; nothing is written, no partial
+ *                                     image (the reference's reservation would have blocked the writer instead)
+ *   4  otherwise                      CAPTURABLE with (hi - lo) x cols floats
+ * `offset` is the exclusive prefix sum of those sizes over all capturable candidates in (slot, order) order.  A capturable
+ * candidate with offset + size <= arena_floats resolves as RO_SNAP_CAPTURED and its rows are copied from their ring slots;
+ * the others -- by the prefix rule the first one that does not fit and every capturable one behind it -- stay pending and
+ * come back in the next call.  Resolved candidates fill d_dir densely in (slot, order) order.  The still-pending ones become
+ * the slot's new pending list in order; those beyond pending_capacity are dropped and counted.  Arena floats past
+ * arena_floats used, directory entries past `resolved` and pending entries past the new counts are not touched.
+ * RO_ERR_INVALID, before anything is launched, the text naming the argument: a null handle, ring (or ring->d_rows),
+ * snapshot_rows, d_pending_count, d_pending (pending_capacity > 0), d_dir or d_snap_summary; d_events == NULL or d_summary ==
+ * NULL with capacity > 0; d_arena == NULL with arena_floats > 0; a negative capacity, pending_capacity, arena_floats or
+ * head_row; a ring as ro_stft_ring_put_resident refuses it; slot_mask 0 or with bits at or above 1 + RO_MAX_EXTRA_BANDS; a
+ * snapshot_rows entry below 1; more than 2^24 candidates in all (the mask's slots x (capacity + pending_capacity)).
+ * Two plain launches (csrc/ro_snapshots.hip: the plan, then the copy), no atomics: equal inputs give equal bytes.  Asynchronous on `stream`; uses
+ * handle scratch (the plan; it grows, waiting for the device, when capacity + pending_capacity grow), so one launch of a
+ * handle in flight at a time unless they share a stream.  ro_stft_run_resident_windows (or the band call),
+ * ro_stft_ring_put_resident, ro_stft_events_resident and this call read nothing on the host: issue them back to back. */
+int ro_stft_snapshots_resident(ro_stft_t *h, const ro_event_t *d_events, int64_t capacity,
+                               const ro_detect_summary_t *d_summary, uint32_t slot_mask, const int32_t *snapshot_rows,
+                               const ro_row_ring_t *ring, int64_t head_row,
+                               ro_event_t *d_pending, int64_t *d_pending_count, int64_t pending_capacity,
+                               ro_snapshot_t *d_dir, float *d_arena, int64_t arena_floats,
+                               ro_snap_summary_t *d_snap_summary, void *stream);
+
+/* The same machine over host memory, candidate by candidate: every pointer is host memory, ring->d_rows included; no
+ * device.  For a host that holds its rows itself (the streaming path), and the yardstick of the device call: equal inputs
+ * give equal bytes in every output.  Refusals as above, without the handle. */
+int ro_snapshots_host(const ro_event_t *events, int64_t capacity, const ro_detect_summary_t *summary, uint32_t slot_mask,
+                      const int32_t *snapshot_rows, const ro_row_ring_t *ring, int64_t head_row,
+                      ro_event_t *pending, int64_t *pending_count, int64_t pending_capacity,
+                      ro_snapshot_t *dir, float *arena, int64_t arena_floats, ro_snap_summary_t *snap_summary);
+
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel
  * when records are requested).  kernel_ms_out (optional, 2 floats) receives the

@@ -74,6 +74,24 @@ DETECT_STATE_DTYPE = np.dtype([("first_detect_row", np.int64), ("last_detect_row
                                ("peak", np.int32), ("magnitude", np.float32), ("open", np.int32)])
 DETECT_SUMMARY_DTYPE = np.dtype([("events", np.int64), ("detect_rows", np.int64), ("marginal_rows", np.int64)])
 
+RO_SNAP_CAPTURED, RO_SNAP_EMPTY, RO_SNAP_LOST = 0, 1, 2
+
+
+class RowRing(C.Structure):
+    """ro_row_ring_t (32 bytes) -- a ring of rows the caller owns: stream row r lives in slot r % ring_rows, `cols` floats
+    of every `stride` (src/WaterfallBackend.cpp:107-127 reserves rows of such a ring for a snapshot)."""
+    _fields_ = [("d_rows", C.c_void_p), ("stride", C.c_int64), ("ring_rows", C.c_int64), ("cols", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+ROW_RING = RowRing
+# ro_snapshot_t (72 bytes: one resolved event) and ro_snap_summary_t (64, one per call)
+SNAPSHOT_DTYPE = np.dtype([("event", EVENT_DTYPE), ("first_row", np.int64), ("offset", np.int64), ("rows", np.int32),
+                           ("slot", np.int32), ("status", np.int32), ("reserved", np.int32)])
+SNAP_SUMMARY_DTYPE = np.dtype([("resolved", np.int64), ("captured", np.int64), ("empty", np.int64), ("lost", np.int64),
+                               ("pending", np.int64), ("pending_dropped", np.int64), ("unlisted", np.int64),
+                               ("arena_floats", np.int64)])
+
 
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bins", C.c_int32), ("overlap", C.c_int32),
@@ -170,6 +188,14 @@ _EXPORTS = {
     "ro_stft_run_resident_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Detector),
                                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ro_stft_ring_put_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(RowRing),
+                                            C.c_void_p]),
+    "ro_stft_snapshots_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32),
+                                             C.POINTER(RowRing), C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ro_snapshots_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(RowRing),
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -443,6 +469,48 @@ def events_host(records, detector, first_row=0, state=None, capacity=None, want_
     return events[:min(int(summary["events"][0]), max(cap, 0))], state, summary[0], detect
 
 
+def _snapshot_rows(snapshot_rows, slot_mask):
+    """one int per slot up to the mask's highest bit (or one int for all of them) -> (ctypes int32 array, slots)"""
+    slots = int(slot_mask).bit_length()
+    if np.isscalar(snapshot_rows):
+        snapshot_rows = [snapshot_rows] * slots
+    if len(snapshot_rows) < slots:
+        raise ValueError("snapshot_rows: one entry per slot up to the mask's highest bit, %d" % slots)
+    return (C.c_int32 * max(slots, 1))(*[int(x) for x in snapshot_rows[:slots]]), slots
+
+
+def snapshots_host(events, summary, slot_mask, snapshot_rows, ring, head_row, pending, pending_count, arena_floats,
+                   cols=None):
+    """The snapshots of one call over host memory -- ro_snapshots_host.  events: EVENT_DTYPE [slots, capacity] and summary:
+    DETECT_SUMMARY_DTYPE [slots] as the events call leaves them (None, None: no events); ring: float32 [ring_rows, stride],
+    stream row r in ring[r % ring_rows], `cols` floats of it (None: stride); pending: EVENT_DTYPE [slots, pending_capacity]
+    and pending_count: int64 [slots], both updated in place.  Returns (directory, arena, summary): the SNAPSHOT_DTYPE
+    entries resolved, the arena floats used, a SNAP_SUMMARY_DTYPE scalar."""
+    rows_arr, slots = _snapshot_rows(snapshot_rows, slot_mask)
+    ring = np.asarray(ring)
+    if ring.dtype != np.float32 or ring.ndim != 2 or not ring.flags.c_contiguous:
+        raise ValueError("ring: a C-contiguous float32 array [ring_rows, stride]")
+    desc = RowRing(ring.ctypes.data, ring.shape[1], ring.shape[0], ring.shape[1] if cols is None else cols, 0)
+    capacity = 0 if events is None else events.shape[1]
+    if events is not None and (events.dtype != EVENT_DTYPE or events.ndim != 2 or events.shape[0] < slots or
+                               not events.flags.c_contiguous or summary is None or summary.dtype != DETECT_SUMMARY_DTYPE or
+                               summary.shape[0] < slots):
+        raise ValueError("events: EVENT_DTYPE [slots, capacity] with summary: DETECT_SUMMARY_DTYPE [slots]")
+    if (pending.dtype != EVENT_DTYPE or pending.ndim != 2 or pending.shape[0] < slots or not pending.flags.c_contiguous or
+            pending_count.dtype != np.int64 or pending_count.shape[0] < slots):
+        raise ValueError("pending: EVENT_DTYPE [slots, pending_capacity] with pending_count: int64 [slots]")
+    pcap = pending.shape[1]
+    directory = np.zeros(max(slots * (capacity + pcap), 1), SNAPSHOT_DTYPE)
+    arena = np.zeros(max(arena_floats, 1), np.float32)
+    out = np.zeros(1, SNAP_SUMMARY_DTYPE)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_snapshots_host(p(events) if capacity else None, capacity, p(summary) if summary is not None else None,
+                                       slot_mask, rows_arr, C.byref(desc), head_row, p(pending) if pcap else None,
+                                       p(pending_count), pcap, p(directory), p(arena) if arena_floats > 0 else None,
+                                       arena_floats, p(out)))
+    return directory[:int(out["resolved"][0])], arena[:int(out["arena_floats"][0])], out[0]
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -587,6 +655,26 @@ class Stft:
                                                      row_stride or self.bins, _ptr(d_tile), _ptr(d_records),
                                                      _ptr(d_extra), _detectors(detectors), _ptr(d_state), _ptr(d_events),
                                                      capacity, _ptr(d_summary), _ptr(d_detect), _ptr(stream)))
+
+    def ring_put_resident(self, d_image, first_row, rows, ring, image_stride=None, stream=None):
+        """rows of d_image (rows x image_stride floats; None: the ring's cols) into the ring's slots: image row i is stream
+        row first_row + i and goes to slot (first_row + i) % ring_rows -- ro_stft_ring_put_resident.  ring: RowRing"""
+        _check(library().ro_stft_ring_put_resident(self._h, _ptr(d_image), ring.cols if image_stride is None else image_stride,
+                                                   first_row, rows, C.byref(ring), _ptr(stream)))
+
+    def snapshots_resident(self, slot_mask, snapshot_rows, ring, head_row, d_pending, d_pending_count, pending_capacity,
+                           d_dir, d_arena, arena_floats, d_snap_summary, d_events=None, capacity=0, d_summary=None,
+                           stream=None):
+        """the rows of every complete event's snapshot out of the ring into d_arena, with a directory; the incomplete ones
+        are carried in d_pending from call to call -- ro_stft_snapshots_resident.  d_events [slot][capacity] (EVENT_DTYPE)
+        and d_summary [slot] as events_resident leaves them; snapshot_rows: one int per slot up to the mask's highest bit,
+        or one for all; d_pending [slots][pending_capacity] events and d_pending_count [slots] int64, zero-filled once;
+        d_dir: slots x (capacity + pending_capacity) SNAPSHOT_DTYPE entries; d_snap_summary: one SNAP_SUMMARY_DTYPE"""
+        rows_arr, _ = _snapshot_rows(snapshot_rows, slot_mask)
+        _check(library().ro_stft_snapshots_resident(self._h, _ptr(d_events), capacity, _ptr(d_summary), slot_mask, rows_arr,
+                                                    C.byref(ring), head_row, _ptr(d_pending), _ptr(d_pending_count),
+                                                    pending_capacity, _ptr(d_dir), _ptr(d_arena), arena_floats,
+                                                    _ptr(d_snap_summary), _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

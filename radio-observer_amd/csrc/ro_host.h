@@ -5,6 +5,7 @@
 //   ro_stream.cpp        push / flush / fetch: staging slots, captured graphs, the row sink
 //   ro_czt.cpp           lengths that are not a power of two (chirp-z on an inner handle)
 //   ro_stft_capi.cpp     create / destroy, the transform launches, the resident entry points
+//   ro_snapshots.cpp     the row ring and the event snapshots cut from it (ro_snapshots.hip)
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
@@ -32,6 +33,7 @@
 #include "ro_band_f64.h"
 #include "ro_band_windows.h"
 #include "ro_events.h"
+#include "ro_snapshots.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -253,6 +255,9 @@ struct ro_stft {
     // their full size (ro::EVENTS_SCRATCH_BYTES, under 0.5 MiB) by the first call -- the block never grows, so no launch
     // ever has to be waited for
     DeviceBlock<char> d_events_scratch;
+    // event snapshots (ro_stft_snapshots_resident): the plan and the compacted pending lists of one call (ro_snapshots.h);
+    // grows with capacity + pending_capacity, and growing frees the old block, which waits for the device
+    DeviceBlock<char> d_snap_scratch;
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
     // belong to (one window for the consecutive call; empty: none); a handle has one precision, so one of the two sets is
@@ -289,6 +294,17 @@ const char *tile_windows_fault(int bins, const ro_band_window_t *w, int count, i
 int tile_windows_check(const char *who, int bins, const ro_band_window_t *w, int count, int64_t *total);
 // the window list and the image of a cut; rows_in / rows / row_stride are filled in by launch_tile_and_scan
 ro::CutArgs make_cut_args(const ro_band_window_t *w, int count, float *d_image, int64_t image_stride);
+
+// what ro_snapshots_host and ro_stft_snapshots_resident ask of their common arguments, as a refusal in the name of `who`;
+// d: "d_" where the arrays are the device's (the argument names of the resident call), "" on the host.  *slots: the mask's
+// highest bit + 1
+int snapshots_check(const char *who, const char *d, const ro_event_t *events, int64_t capacity,
+                    const ro_detect_summary_t *summary, uint32_t slot_mask, const int32_t *snapshot_rows,
+                    const ro_row_ring_t *ring, int64_t head_row, const ro_event_t *pending, const int64_t *pending_count,
+                    int64_t pending_capacity, const ro_snapshot_t *dir, const float *arena, int64_t arena_floats,
+                    const ro_snap_summary_t *snap_summary, int *slots);
+// ... and of a ring (null: refused too)
+int ring_check(const char *who, const ro_row_ring_t *ring);
 
 // ---- ro_stft_capi.cpp
 ro::StftArgs make_stft_args(const ro_stft *h, const void *d_iq, int64_t first_row, int64_t rows, float *d_rows,
