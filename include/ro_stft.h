@@ -627,6 +627,103 @@ int ro_snapshots_host(const ro_event_t *events, int64_t capacity, const ro_detec
                       ro_event_t *pending, int64_t *pending_count, int64_t pending_capacity,
                       ro_snapshot_t *dir, float *arena, int64_t arena_floats, ro_snap_summary_t *snap_summary);
 
+/* ---- raw I/Q of each event: cut from the resident samples --------------------------
+ * The other half of what the METEOR DETECTED branch writes: it sets includeRawData (src/BolidRecorder.cpp:262), and the
+ * worker writes the I/Q samples behind the image as a 2 x L float image (writeRaw(), src/WaterfallBackend.cpp:77-81,
+ * :214-267).  One call per chunk reads the snapshot directory where ro_stft_snapshots_resident left it and cuts each
+ * captured event's samples out of the sample buffers the transform read, as (float)re, (float)im pairs
+ * (FFTBackend::floatToInt, src/FFTBackend.h:250-254: the sample as delivered, before the I/Q gain), into an arena with a
+ * directory.  There is no sample ring: the caller names the buffers that still hold the samples. */
+#define RO_MAX_IQ_SPANS 4
+typedef struct ro_iq_span {        /* 32 bytes: stream samples [first_sample, first_sample + samples) lie at d_iq */
+    const void *d_iq;              /* device (host memory for ro_raw_host), in `format`, aligned to 8 bytes (RO_IQ_I16: 4) */
+    int64_t     first_sample;      /* >= 0: unwrapped index into the stream */
+    int64_t     samples;           /* >= 1 */
+    int32_t     format;            /* RO_IQ_F32, RO_IQ_I16 or RO_IQ_F64, on any handle */
+    int32_t     reserved;          /* 0 */
+} ro_iq_span_t;
+
+typedef struct ro_raw_capture {    /* 72 bytes: one resolved candidate */
+    ro_event_t event;              /* as the snapshot directory held it */
+    int64_t    first_sample;       /* f, below */
+    int64_t    samples;            /* L if CAPTURED, else 0 */
+    int64_t    offset;             /* floats into d_arena: `samples` pairs re, im; 0 unless CAPTURED */
+    int32_t    slot;
+    int32_t    status;             /* RO_SNAP_CAPTURED / RO_SNAP_EMPTY / RO_SNAP_LOST */
+} ro_raw_capture_t;
+
+typedef struct ro_raw_summary {    /* 64 bytes, overwritten by every call */
+    int64_t resolved;              /* entries written to d_raw_dir */
+    int64_t captured, empty, lost; /* of those, by status */
+    int64_t pending;               /* entries in the pending list after the call */
+    int64_t pending_dropped;       /* candidates that found no room in it: gone, counted here */
+    int64_t arena_floats;          /* floats of d_arena used */
+    int64_t reserved;              /* 0 */
+} ro_raw_summary_t;
+
+/* The raw runs of one call.
+ *   d_dir, dir_capacity, d_snap_summary   the directory and the summary of ro_stft_snapshots_resident, as it leaves them;
+ *                    the number of entries is read ON THE DEVICE: min(d_snap_summary->resolved, dir_capacity), at least 0
+ *   spans, span_count   HOST array of 1 ... RO_MAX_IQ_SPANS buffers that hold the stream's samples (it travels in the
+ *                    kernel arguments).  first_sample and first_sample + samples both ascend strictly from span to span,
+ *                    and each span begins at or before the end of the one in front: no gap, overlap allowed (the chunk
+ *                    buffers of a resident run overlap by bins - hop samples).  A sample several spans hold is read from
+ *                    the LAST one that holds it.  base_sample = spans[0].first_sample, head_sample = the end of the last
+ *                    span.  A host that double-buffers its uploads passes its last two or three chunk buffers
+ *   d_pending, d_pending_count   ONE list of pending_capacity ro_snapshot_t and one count, in / out, zero-filled by the
+ *                    caller once (a count outside [0, pending_capacity] is read as the nearer bound); d_pending may be
+ *                    NULL with pending_capacity = 0
+ *   d_raw_dir        room for pending_capacity + dir_capacity entries, so it cannot overflow
+ *   d_arena          arena_floats floats, aligned to 8 bytes; NULL with arena_floats = 0
+ *   d_raw_summary    one entry
+ * The CANDIDATES are the pending list, in order (every entry of it), followed by the directory's entries whose status is
+ * RO_SNAP_CAPTURED, in order.  EMPTY and LOST directory entries have no image and get no raw run: skipped, not resolved.
+ * For a candidate c, with hop = bins - overlap of the handle (the clamped overlap) and z = (overlap == 0):
+ *   start = c.event.start_row,  len = c.rows + (c.first_row - start)   the clamped length, also when the image was clipped
+ *                                                                      at row 0
+ *   L = (int64)(((double)len / (double)R) * (double)sample_rate),  R = (int)ro_fft_sample_rate(...): one division, one
+ *       multiplication, truncated toward zero -- the recorder's fftSamplesToRaw (src/WaterfallBackend.h:84-87,
+ *       src/WaterfallBackend.cpp:29-32: the rate is truncated to an int)
+ *   f = (start - z) * hop + 1 for start >= 1, else 0 -- fftMarkToRaw(start): the handle at `start` was stamped by row
+ *       start - 1 with the raw mark one slot ahead (src/WaterfallBackend.cpp:507), read after the overlap memmove
+ *       (src/FFTBackend.cpp:242,251); on a fresh stream nobody has stamped the handles at or below 0 (mark 0)
+ * and, in this order:
+ *   1  f + L > head_sample            still PENDING: not resolved (the reference would write stale ring contents; L
+ *                                     exceeds len x hop by up to fft rate / R, so this is no corner case)
+ *   2  L <= 0                         resolves as RO_SNAP_EMPTY
+ *   3  f < base_sample                resolves as RO_SNAP_LOST: nothing is written
+ *   4  otherwise                      CAPTURABLE with 2 L floats
+ * `offset` is the exclusive prefix sum of those sizes over all capturable candidates in order.  A capturable candidate
+ * with offset + 2 L <= arena_floats resolves as RO_SNAP_CAPTURED and its samples are converted into the arena: RO_IQ_F32 a
+ * bit copy, RO_IQ_I16 (float) of each int16, RO_IQ_F64 (float) of each double, round to nearest even (a result that is a
+ * float32 denormal is not pinned).  No gain.  The others -- the first that does not fit and every capturable one behind it
+ * -- stay pending.  Resolved candidates fill d_raw_dir densely, in order; the still-pending ones become the new list, in
+ * order, those beyond pending_capacity dropped and counted.  Arena floats past arena_floats used, directory entries past
+ * `resolved` and pending entries past the new count are not touched; neither are the sample buffers and d_dir.
+ * RO_ERR_INVALID, before anything is launched, the text naming the argument: a null handle, d_snap_summary, spans,
+ * d_pending_count, d_raw_dir or d_raw_summary; d_dir == NULL with dir_capacity > 0; d_pending == NULL with
+ * pending_capacity > 0; d_arena == NULL with arena_floats > 0 (or misaligned); a negative dir_capacity, pending_capacity or
+ * arena_floats; span_count outside 1 ... RO_MAX_IQ_SPANS; a span with d_iq NULL (or misaligned), first_sample < 0,
+ * samples < 1, an unknown format or reserved != 0; spans out of order or with a gap; more than 2^24 candidates
+ * (pending_capacity + dir_capacity).  RO_ERR_UNSUPPORTED when R is 0 (the reference divides by zero there).
+ * Two plain launches (csrc/ro_raw.hip: the plan, then the copy), no atomics: equal inputs give equal bytes.  Asynchronous
+ * on `stream`; uses handle scratch (the plan; it grows, waiting for the device, when pending_capacity + dir_capacity
+ * grow).  Nothing is read on the host: a chunk is ro_stft_run_resident_windows, ro_stft_ring_put_resident,
+ * ro_stft_events_resident, ro_stft_snapshots_resident and this call, issued back to back. */
+int ro_stft_raw_resident(ro_stft_t *h, const ro_snapshot_t *d_dir, int64_t dir_capacity,
+                         const ro_snap_summary_t *d_snap_summary, const ro_iq_span_t *spans, int span_count,
+                         ro_snapshot_t *d_pending, int64_t *d_pending_count, int64_t pending_capacity,
+                         ro_raw_capture_t *d_raw_dir, float *d_arena, int64_t arena_floats,
+                         ro_raw_summary_t *d_raw_summary, void *stream);
+
+/* The same machine over host memory, candidate by candidate: every pointer is host memory, the spans' d_iq included; no
+ * handle, no device (bins >= 2, overlap and sample_rate as ro_fft_sample_rate takes them).  The yardstick of the device
+ * call: equal inputs give equal bytes in every output.  Refusals as above, without the handle and the alignments. */
+int ro_raw_host(int bins, int overlap, int sample_rate, const ro_snapshot_t *dir, int64_t dir_capacity,
+                const ro_snap_summary_t *snap_summary, const ro_iq_span_t *spans, int span_count,
+                ro_snapshot_t *pending, int64_t *pending_count, int64_t pending_capacity,
+                ro_raw_capture_t *raw_dir, float *arena, int64_t arena_floats, ro_raw_summary_t *raw_summary);
+
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel
  * when records are requested).  kernel_ms_out (optional, 2 floats) receives the

@@ -20,6 +20,7 @@ from .capi import (  # noqa: F401
     tile_windows_supported, merge_windows, events_host, Detector,
     EVENT_DTYPE, DETECT_STATE_DTYPE, DETECT_SUMMARY_DTYPE,
     snapshots_host, RowRing, ROW_RING, SNAPSHOT_DTYPE, SNAP_SUMMARY_DTYPE, RO_SNAP_CAPTURED, RO_SNAP_EMPTY, RO_SNAP_LOST,
+    raw_host, IqSpan, RAW_CAPTURE_DTYPE, RAW_SUMMARY_DTYPE, RO_MAX_IQ_SPANS,
     RO_WINDOW_NUTTALL, RO_WINDOW_HANN, RO_WINDOW_CUSTOM, RO_IQ_F32, RO_IQ_I16, RO_IQ_F64,
     RO_PRECISION_F32, RO_PRECISION_F64,
 )

@@ -93,6 +93,23 @@ SNAP_SUMMARY_DTYPE = np.dtype([("resolved", np.int64), ("captured", np.int64), (
                                ("arena_floats", np.int64)])
 
 
+RO_MAX_IQ_SPANS = 4
+
+
+class IqSpan(C.Structure):
+    """ro_iq_span_t (32 bytes) -- stream samples [first_sample, first_sample + samples) lie at d_iq, in `format`"""
+    _fields_ = [("d_iq", C.c_void_p), ("first_sample", C.c_int64), ("samples", C.c_int64), ("format", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# ro_raw_capture_t (72 bytes: one resolved candidate of the raw capture) and ro_raw_summary_t (64, one per call)
+RAW_CAPTURE_DTYPE = np.dtype([("event", EVENT_DTYPE), ("first_sample", np.int64), ("samples", np.int64), ("offset", np.int64),
+                              ("slot", np.int32), ("status", np.int32)])
+RAW_SUMMARY_DTYPE = np.dtype([("resolved", np.int64), ("captured", np.int64), ("empty", np.int64), ("lost", np.int64),
+                              ("pending", np.int64), ("pending_dropped", np.int64), ("arena_floats", np.int64),
+                              ("reserved", np.int64)])
+
+
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bins", C.c_int32), ("overlap", C.c_int32),
                 ("sample_rate", C.c_int32), ("window_kind", C.c_int32),
@@ -196,6 +213,10 @@ _EXPORTS = {
     "ro_snapshots_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(RowRing),
                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_void_p]),
+    "ro_stft_raw_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(IqSpan), C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ro_raw_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(IqSpan), C.c_int,
+                              C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -511,6 +532,45 @@ def snapshots_host(events, summary, slot_mask, snapshot_rows, ring, head_row, pe
     return directory[:int(out["resolved"][0])], arena[:int(out["arena_floats"][0])], out[0]
 
 
+def _spans(spans):
+    """IqSpan or (address, first_sample, samples, format) each -> (ctypes array, count)"""
+    spans = list(spans)
+    arr = (IqSpan * max(len(spans), 1))()
+    for i, sp in enumerate(spans):
+        arr[i] = sp if isinstance(sp, IqSpan) else IqSpan(None if sp[0] is None else _ptr(sp[0]).value, sp[1], sp[2], sp[3], 0)
+    return arr, len(spans)
+
+
+def raw_host(bins, overlap, sample_rate, directory, snap_summary, spans, pending, pending_count, arena_floats):
+    """The raw I/Q runs of one call over host memory -- ro_raw_host.  directory: SNAPSHOT_DTYPE entries and snap_summary: a
+    SNAP_SUMMARY_DTYPE array of one entry, as the snapshots call leaves them; spans: [(array, first_sample, format), ...] of
+    numpy arrays that hold whole samples (float32 / int16 / float64, two numbers each); pending: SNAPSHOT_DTYPE
+    [pending_capacity] and pending_count: int64 [1], both updated in place.  Returns (raw directory, arena, summary): the
+    RAW_CAPTURE_DTYPE entries resolved, the arena floats used, a RAW_SUMMARY_DTYPE scalar."""
+    directory = np.ascontiguousarray(directory)
+    if directory.dtype != SNAPSHOT_DTYPE or directory.ndim != 1 or snap_summary.dtype != SNAP_SUMMARY_DTYPE:
+        raise ValueError("directory: SNAPSHOT_DTYPE [n] with snap_summary: SNAP_SUMMARY_DTYPE [1]")
+    if (pending.dtype != SNAPSHOT_DTYPE or pending.ndim != 1 or not pending.flags.c_contiguous or
+            pending_count.dtype != np.int64 or pending_count.size < 1):
+        raise ValueError("pending: SNAPSHOT_DTYPE [pending_capacity] with pending_count: int64 [1]")
+    item = {RO_IQ_F32: 8, RO_IQ_I16: 4, RO_IQ_F64: 16}
+    keep, desc = [], []
+    for array, first_sample, fmt in spans:
+        array = np.ascontiguousarray(array)
+        keep.append(array)
+        desc.append(IqSpan(array.ctypes.data, first_sample, array.nbytes // item.get(fmt, 8), fmt, 0))
+    arr, count = _spans(desc)
+    dcap, pcap = directory.shape[0], pending.shape[0]
+    raw_dir = np.zeros(max(dcap + pcap, 1), RAW_CAPTURE_DTYPE)
+    arena = np.zeros(max(arena_floats, 1), np.float32)
+    out = np.zeros(1, RAW_SUMMARY_DTYPE)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_raw_host(bins, overlap, sample_rate, p(directory) if dcap else None, dcap, p(snap_summary), arr, count,
+                                 p(pending) if pcap else None, p(pending_count), pcap, p(raw_dir),
+                                 p(arena) if arena_floats > 0 else None, arena_floats, p(out)))
+    return raw_dir[:int(out["resolved"][0])], arena[:int(out["arena_floats"][0])], out[0]
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -675,6 +735,19 @@ class Stft:
                                                     C.byref(ring), head_row, _ptr(d_pending), _ptr(d_pending_count),
                                                     pending_capacity, _ptr(d_dir), _ptr(d_arena), arena_floats,
                                                     _ptr(d_snap_summary), _ptr(stream)))
+
+    def raw_resident(self, d_dir, dir_capacity, d_snap_summary, spans, d_pending, d_pending_count, pending_capacity,
+                     d_raw_dir, d_arena, arena_floats, d_raw_summary, stream=None):
+        """the I/Q samples behind every captured snapshot of d_dir, cut out of the sample buffers `spans` names and packed as
+        (float)re, (float)im pairs into d_arena, with a directory; the runs whose samples have not all arrived are carried
+        in d_pending from call to call -- ro_stft_raw_resident.  d_dir [dir_capacity] (SNAPSHOT_DTYPE) and d_snap_summary
+        as snapshots_resident leaves them; spans: up to RO_MAX_IQ_SPANS of IqSpan or (d_iq, first_sample, samples, format),
+        ascending, without a gap; d_pending [pending_capacity] SNAPSHOT_DTYPE and d_pending_count, one int64, zero-filled
+        once; d_raw_dir: pending_capacity + dir_capacity RAW_CAPTURE_DTYPE entries; d_raw_summary: one RAW_SUMMARY_DTYPE"""
+        arr, count = _spans(spans)
+        _check(library().ro_stft_raw_resident(self._h, _ptr(d_dir), dir_capacity, _ptr(d_snap_summary), arr, count,
+                                              _ptr(d_pending), _ptr(d_pending_count), pending_capacity, _ptr(d_raw_dir),
+                                              _ptr(d_arena), arena_floats, _ptr(d_raw_summary), _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

@@ -6,6 +6,7 @@
 //   ro_czt.cpp           lengths that are not a power of two (chirp-z on an inner handle)
 //   ro_stft_capi.cpp     create / destroy, the transform launches, the resident entry points
 //   ro_snapshots.cpp     the row ring and the event snapshots cut from it (ro_snapshots.hip)
+//   ro_raw.cpp           the raw I/Q of each event, cut from the resident samples (ro_raw.hip), and its host twin
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
@@ -34,6 +35,7 @@
 #include "ro_band_windows.h"
 #include "ro_events.h"
 #include "ro_snapshots.h"
+#include "ro_raw.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -258,6 +260,9 @@ struct ro_stft {
     // event snapshots (ro_stft_snapshots_resident): the plan and the compacted pending lists of one call (ro_snapshots.h);
     // grows with capacity + pending_capacity, and growing frees the old block, which waits for the device
     DeviceBlock<char> d_snap_scratch;
+    // raw I/Q of the events (ro_stft_raw_resident): the plan of one call (ro_raw.h); grows with pending_capacity +
+    // dir_capacity, like the block above
+    DeviceBlock<char> d_raw_scratch;
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
     // belong to (one window for the consecutive call; empty: none); a handle has one precision, so one of the two sets is
