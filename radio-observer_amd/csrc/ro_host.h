@@ -258,7 +258,7 @@ struct ro_stft {
     // ever has to be waited for
     DeviceBlock<char> d_events_scratch;
     // event snapshots (ro_stft_snapshots_resident): the plan and the compacted pending lists of one call (ro_snapshots.h);
-    // grows with capacity + pending_capacity, and growing frees the old block, which waits for the device
+    // grows with capacity + pending_capacity; the regrow waits for the device before the old block goes
     DeviceBlock<char> d_snap_scratch;
     // raw I/Q of the events (ro_stft_raw_resident): the plan of one call (ro_raw.h); grows with pending_capacity +
     // dir_capacity, like the block above

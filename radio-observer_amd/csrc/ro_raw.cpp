@@ -88,7 +88,10 @@ extern "C" int ro_stft_raw_resident(ro_stft_t *h, const ro_snapshot_t *d_dir, in
     if ((rc = raw_rate(who, h->cfg.sample_rate, h->bins, h->cfg.overlap, &rate_r)) != RO_OK) return rc;
     HIP_TRY(hipSetDevice(h->device));
     const size_t need = ro::raw_scratch_bytes(dir_capacity, pending_capacity);
-    if (h->d_raw_scratch.count() < need) HIP_TRY(h->d_raw_scratch.alloc(need));
+    if (h->d_raw_scratch.count() < need) {
+        if (h->d_raw_scratch) HIP_TRY(hipDeviceSynchronize());   // (an earlier launch may still be using the old block)
+        HIP_TRY(h->d_raw_scratch.alloc(need));
+    }
     ro::RawArgs a{};
     a.dir = d_dir;
     a.snap_summary = d_snap_summary;

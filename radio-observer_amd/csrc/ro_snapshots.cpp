@@ -51,7 +51,10 @@ extern "C" int ro_stft_snapshots_resident(ro_stft_t *h, const ro_event_t *d_even
     if (rc != RO_OK) return rc;
     HIP_TRY(hipSetDevice(h->device));
     const size_t need = ro::snap_scratch_bytes(slots, capacity, pending_capacity);
-    if (h->d_snap_scratch.count() < need) HIP_TRY(h->d_snap_scratch.alloc(need));
+    if (h->d_snap_scratch.count() < need) {
+        if (h->d_snap_scratch) HIP_TRY(hipDeviceSynchronize());   // (an earlier launch may still be using the old block)
+        HIP_TRY(h->d_snap_scratch.alloc(need));
+    }
     ro::SnapArgs a{};
     a.events = d_events;
     a.summary = d_summary;
