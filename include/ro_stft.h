@@ -724,6 +724,94 @@ int ro_raw_host(int bins, int overlap, int sample_rate, const ro_snapshot_t *dir
                 ro_snapshot_t *pending, int64_t *pending_count, int64_t pending_capacity,
                 ro_raw_capture_t *raw_dir, float *arena, int64_t arena_floats, ro_raw_summary_t *raw_summary);
 
+/* ---- event files: FITS data units cut to each recorder's columns -------------------
+ * What is left between the two arenas above and the files: the worker writes rightBin_ - leftBin_ columns of every row for
+ * the ONE recorder that fired (src/WaterfallBackend.cpp:176-177, :202-205; the raw image is 2 x L, :235, :258-261), and
+ * FITSWriter stores every float big-endian and pads the data unit with zeros to a multiple of 2880 bytes
+ * (src/FITSWriter.cpp).  One call per arena reads the directory where ro_stft_snapshots_resident (ro_stft_raw_resident) left
+ * it and packs, for every captured entry, the data unit of its file: cut to the slot's columns, every float's four bytes
+ * reversed, zero-padded to the block.  A host downloads the units in use, writes a header and makes one fwrite per file.
+ * Headers, names, times and [compress] stay host work. */
+#define RO_FITS_BLOCK 2880                     /* bytes; 720 floats */
+enum { RO_UNIT_WRITTEN = 0, RO_UNIT_SKIPPED = 1, RO_UNIT_NO_ROOM = 2, RO_UNIT_INVALID = 3 };
+
+typedef struct ro_fits_unit {      /* 32 bytes; entry d belongs to entry d of the source directory */
+    int64_t offset;                /* bytes into d_units, a multiple of 2880; 0 unless WRITTEN */
+    int64_t bytes;                 /* 4 * naxis1 * naxis2: the data; the unit occupies this rounded up to 2880 */
+    int64_t naxis2;                /* rows (images) or samples (raw) */
+    int32_t naxis1;                /* the slot's window cols (images) or 2 (raw) */
+    int32_t status;                /* RO_UNIT_* */
+} ro_fits_unit_t;
+
+typedef struct ro_unit_summary {   /* 64 bytes, overwritten by every call */
+    int64_t entries, written, skipped, no_room, invalid;
+    int64_t units_bytes;           /* end of the last WRITTEN unit */
+    int64_t needed_bytes;          /* 2880 * the blocks of ALL writable entries: the room that holds everything */
+    int64_t reserved;              /* 0 */
+} ro_unit_summary_t;
+
+/* The data units of one snapshot arena.
+ *   d_dir, dir_capacity, d_snap_summary   the directory and the summary of ro_stft_snapshots_resident, as it leaves them;
+ *                    the number of entries is read ON THE DEVICE: n = min(max(d_snap_summary->resolved, 0), dir_capacity)
+ *   d_arena, arena_floats, cols   the arena that call filled, and the floats of one of its rows (the ring's cols); NULL
+ *                    with arena_floats = 0
+ *   slot_windows     HOST array of 1 + RO_MAX_EXTRA_BANDS entries (it travels in the kernel arguments): where slot s's
+ *                    recorder's columns sit in the IMAGE -- first_col = ro_merge_windows' offsets_out[i], cols = ranges[i].cols
+ *                    -- or cols = 0: this recorder's files are not wanted
+ *   d_unit_dir       room for dir_capacity entries; entry d describes d_dir[d], for d < n; entries at or behind n are not
+ *                    touched
+ *   d_units, units_bytes   the units, aligned to 16 bytes; NULL with units_bytes = 0
+ *   d_unit_summary   one entry
+ * For entry d < n, in this order:
+ *   1  status != RO_SNAP_CAPTURED      RO_UNIT_SKIPPED
+ *   2  slot outside [0, 1 + RO_MAX_EXTRA_BANDS), rows < 1, offset < 0, or offset + rows x cols > arena_floats
+ *                                      RO_UNIT_INVALID: not what the producing call writes; nothing of it is read from the arena
+ *   3  the slot's window has cols == 0 RO_UNIT_SKIPPED
+ *   4  otherwise                       WRITABLE: naxis1 = the window's cols, naxis2 = rows, bytes = 4 naxis1 naxis2,
+ *                                      blocks = ceil(bytes / 2880)
+ * `offset` is 2880 x the exclusive prefix sum of `blocks` over all writable entries in directory order, fitting or not (the
+ * snapshots' prefix rule: nothing behind the first entry that does not fit can fit).  A writable entry with offset +
+ * 2880 blocks <= units_bytes is RO_UNIT_WRITTEN, the others RO_UNIT_NO_ROOM: they carry naxis1, naxis2 and bytes, with offset
+ * 0, so that the host can size a second call from them and from needed_bytes.  SKIPPED and INVALID entries are zero but for
+ * the status.  A written unit: float i = r naxis1 + c is arena float offset + r cols + first_col + c with its four bytes
+ * reversed -- a bit copy: NaN payloads, -0 and denormals survive -- and the bytes from `bytes` to the end of the last
+ * block are zero.  Bytes of d_units past the summary's units_bytes are not touched.  Nothing is remembered and the sources
+ * are not written: a call can be repeated with a larger d_units, and a directory built by hand over any packed image gives
+ * the periodic SnapshotRecorder the same service.  n == 0 is RO_OK with a zero summary.
+ * RO_ERR_INVALID, before anything is launched, the text naming the argument: a null handle, d_snap_summary, slot_windows,
+ * d_unit_dir or d_unit_summary; d_dir == NULL with dir_capacity > 0; d_arena == NULL with arena_floats > 0; d_units == NULL
+ * with units_bytes > 0; d_units not aligned to 16 bytes; a negative dir_capacity, arena_floats or units_bytes; dir_capacity >
+ * 2^24; cols < 1; a slot window with first_col < 0, cols < 0 or first_col + cols > cols; [d_units, + units_bytes)
+ * overlapping the arena.
+ * Two plain launches (csrc/ro_units.hip: the plan, then the copy), no atomics: equal inputs give equal bytes.  Asynchronous
+ * on `stream`; uses handle scratch (the plan; it grows, waiting for the device, when dir_capacity grows) -- this call and
+ * ro_stft_raw_units_resident each have a block of their own, so the two of a chunk may run on different streams; two calls of
+ * the SAME kind on one handle share theirs: one in flight at a time unless they share a stream.  Nothing is read
+ * on the host: a chunk is ... ro_stft_snapshots_resident, ro_stft_raw_resident and the two calls here, issued back to back. */
+int ro_stft_snapshot_units_resident(ro_stft_t *h, const ro_snapshot_t *d_dir, int64_t dir_capacity,
+                                    const ro_snap_summary_t *d_snap_summary, const float *d_arena, int64_t arena_floats,
+                                    int32_t cols, const ro_band_window_t *slot_windows,
+                                    ro_fits_unit_t *d_unit_dir, void *d_units, int64_t units_bytes,
+                                    ro_unit_summary_t *d_unit_summary, void *stream);
+
+/* The data units of one raw arena: the same with the directory and the summary of ro_stft_raw_resident.  An entry is
+ * INVALID with samples < 1, offset < 0 or offset + 2 samples > arena_floats; there is no slot window: naxis1 = 2,
+ * naxis2 = samples, and float i of the unit is arena float offset + i.  Refusals as above, without cols and slot_windows
+ * (null d_raw_summary). */
+int ro_stft_raw_units_resident(ro_stft_t *h, const ro_raw_capture_t *d_raw_dir, int64_t dir_capacity,
+                               const ro_raw_summary_t *d_raw_summary, const float *d_arena, int64_t arena_floats,
+                               ro_fits_unit_t *d_unit_dir, void *d_units, int64_t units_bytes,
+                               ro_unit_summary_t *d_unit_summary, void *stream);
+
+/* The same rules over host memory, entry by entry: every pointer is host memory; no handle, no device.  The yardstick of
+ * the device calls: equal inputs give equal bytes in every output.  Refusals as above, without the handle and the alignment. */
+int ro_snapshot_units_host(const ro_snapshot_t *dir, int64_t dir_capacity, const ro_snap_summary_t *snap_summary,
+                           const float *arena, int64_t arena_floats, int32_t cols, const ro_band_window_t *slot_windows,
+                           ro_fits_unit_t *unit_dir, void *units, int64_t units_bytes, ro_unit_summary_t *unit_summary);
+int ro_raw_units_host(const ro_raw_capture_t *raw_dir, int64_t dir_capacity, const ro_raw_summary_t *raw_summary,
+                      const float *arena, int64_t arena_floats,
+                      ro_fits_unit_t *unit_dir, void *units, int64_t units_bytes, ro_unit_summary_t *unit_summary);
+
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel
  * when records are requested).  kernel_ms_out (optional, 2 floats) receives the

@@ -21,6 +21,8 @@ from .capi import (  # noqa: F401
     EVENT_DTYPE, DETECT_STATE_DTYPE, DETECT_SUMMARY_DTYPE,
     snapshots_host, RowRing, ROW_RING, SNAPSHOT_DTYPE, SNAP_SUMMARY_DTYPE, RO_SNAP_CAPTURED, RO_SNAP_EMPTY, RO_SNAP_LOST,
     raw_host, IqSpan, RAW_CAPTURE_DTYPE, RAW_SUMMARY_DTYPE, RO_MAX_IQ_SPANS,
+    snapshot_units_host, raw_units_host, FITS_UNIT_DTYPE, UNIT_SUMMARY_DTYPE, RO_FITS_BLOCK,
+    RO_UNIT_WRITTEN, RO_UNIT_SKIPPED, RO_UNIT_NO_ROOM, RO_UNIT_INVALID,
     RO_WINDOW_NUTTALL, RO_WINDOW_HANN, RO_WINDOW_CUSTOM, RO_IQ_F32, RO_IQ_I16, RO_IQ_F64,
     RO_PRECISION_F32, RO_PRECISION_F64,
 )

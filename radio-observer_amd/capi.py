@@ -109,6 +109,15 @@ RAW_SUMMARY_DTYPE = np.dtype([("resolved", np.int64), ("captured", np.int64), ("
                               ("pending", np.int64), ("pending_dropped", np.int64), ("arena_floats", np.int64),
                               ("reserved", np.int64)])
 
+RO_FITS_BLOCK = 2880
+RO_UNIT_WRITTEN, RO_UNIT_SKIPPED, RO_UNIT_NO_ROOM, RO_UNIT_INVALID = 0, 1, 2, 3
+# ro_fits_unit_t (32 bytes: the data unit of source directory entry d) and ro_unit_summary_t (64, one per call)
+FITS_UNIT_DTYPE = np.dtype([("offset", np.int64), ("bytes", np.int64), ("naxis2", np.int64), ("naxis1", np.int32),
+                            ("status", np.int32)])
+UNIT_SUMMARY_DTYPE = np.dtype([("entries", np.int64), ("written", np.int64), ("skipped", np.int64), ("no_room", np.int64),
+                               ("invalid", np.int64), ("units_bytes", np.int64), ("needed_bytes", np.int64),
+                               ("reserved", np.int64)])
+
 
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bins", C.c_int32), ("overlap", C.c_int32),
@@ -217,6 +226,15 @@ _EXPORTS = {
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ro_raw_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(IqSpan), C.c_int,
                               C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ro_stft_snapshot_units_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                                  C.POINTER(BandWindow), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_void_p]),
+    "ro_stft_raw_units_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ro_snapshot_units_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.POINTER(BandWindow), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ro_raw_units_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_void_p]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -571,6 +589,52 @@ def raw_host(bins, overlap, sample_rate, directory, snap_summary, spans, pending
     return raw_dir[:int(out["resolved"][0])], arena[:int(out["arena_floats"][0])], out[0]
 
 
+def _slot_windows(slot_windows):
+    """BandWindow or (first_col, cols) per slot, None for a slot whose files are not wanted -> a ctypes array of
+    1 + RO_MAX_EXTRA_BANDS windows (the slots that are not named: not wanted)"""
+    slot_windows = list(slot_windows)
+    if len(slot_windows) > 1 + RO_MAX_EXTRA_BANDS:
+        raise ValueError("slot_windows: at most one per slot, %d" % (1 + RO_MAX_EXTRA_BANDS))
+    arr = (BandWindow * (1 + RO_MAX_EXTRA_BANDS))()
+    for i, w in enumerate(slot_windows):
+        if w is not None:
+            arr[i] = w if isinstance(w, BandWindow) else BandWindow(int(w[0]), int(w[1]))
+    return arr
+
+
+def _units_host(call, directory, dtype, summary, arena, units_bytes, *middle):
+    directory = np.ascontiguousarray(directory)
+    if directory.dtype != dtype or directory.ndim != 1 or summary.itemsize != 64 or summary.size < 1:
+        raise ValueError("directory: %d-byte entries [n] with the summary of the call that wrote them" % dtype.itemsize)
+    arena = np.ascontiguousarray(arena)
+    if arena.dtype != np.float32 or arena.ndim != 1:
+        raise ValueError("arena: float32 [arena_floats]")
+    dcap = directory.shape[0]
+    unit_dir = np.zeros(max(dcap, 1), FITS_UNIT_DTYPE)
+    units = np.zeros(max(units_bytes, 1), np.uint8)
+    out = np.zeros(1, UNIT_SUMMARY_DTYPE)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(call(p(directory) if dcap else None, dcap, p(summary), p(arena) if arena.size else None, arena.size, *middle,
+                p(unit_dir), p(units) if units_bytes > 0 else None, units_bytes, p(out)))
+    return unit_dir[:int(out["entries"][0])], units[:int(out["units_bytes"][0])], out[0]
+
+
+def snapshot_units_host(directory, snap_summary, arena, cols, slot_windows, units_bytes):
+    """The FITS data units of one snapshot arena over host memory -- ro_snapshot_units_host.  directory: SNAPSHOT_DTYPE
+    entries and snap_summary: a SNAP_SUMMARY_DTYPE array of one entry, as the snapshots call leaves them; arena: float32,
+    rows of `cols` floats; slot_windows: (first_col, cols) of each slot's recorder in the image, None: not wanted.
+    Returns (unit directory, units, summary): one FITS_UNIT_DTYPE entry per directory entry, the bytes of the units in
+    use, a UNIT_SUMMARY_DTYPE scalar."""
+    return _units_host(library().ro_snapshot_units_host, directory, SNAPSHOT_DTYPE, snap_summary, arena, units_bytes, cols,
+                       _slot_windows(slot_windows))
+
+
+def raw_units_host(raw_directory, raw_summary, arena, units_bytes):
+    """The FITS data units of one raw arena over host memory -- ro_raw_units_host.  raw_directory: RAW_CAPTURE_DTYPE entries
+    and raw_summary: a RAW_SUMMARY_DTYPE array of one entry, as the raw call leaves them.  Returns as snapshot_units_host."""
+    return _units_host(library().ro_raw_units_host, raw_directory, RAW_CAPTURE_DTYPE, raw_summary, arena, units_bytes)
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -748,6 +812,26 @@ class Stft:
         _check(library().ro_stft_raw_resident(self._h, _ptr(d_dir), dir_capacity, _ptr(d_snap_summary), arr, count,
                                               _ptr(d_pending), _ptr(d_pending_count), pending_capacity, _ptr(d_raw_dir),
                                               _ptr(d_arena), arena_floats, _ptr(d_raw_summary), _ptr(stream)))
+
+    def snapshot_units_resident(self, d_dir, dir_capacity, d_snap_summary, d_arena, arena_floats, cols, slot_windows,
+                                d_unit_dir, d_units, units_bytes, d_unit_summary, stream=None):
+        """the FITS data unit of every captured image of d_dir: cut to its slot's columns, big-endian, zero-padded to 2880
+        bytes, packed into d_units with a directory -- ro_stft_snapshot_units_resident.  d_dir [dir_capacity]
+        (SNAPSHOT_DTYPE), d_snap_summary and d_arena (rows of `cols` floats) as snapshots_resident leaves them;
+        slot_windows: (first_col, cols) of each slot's recorder in the image, None: not wanted; d_unit_dir: dir_capacity
+        FITS_UNIT_DTYPE entries; d_units: units_bytes bytes, aligned to 16; d_unit_summary: one UNIT_SUMMARY_DTYPE"""
+        _check(library().ro_stft_snapshot_units_resident(self._h, _ptr(d_dir), dir_capacity, _ptr(d_snap_summary), _ptr(d_arena),
+                                                         arena_floats, cols, _slot_windows(slot_windows), _ptr(d_unit_dir),
+                                                         _ptr(d_units), units_bytes, _ptr(d_unit_summary), _ptr(stream)))
+
+    def raw_units_resident(self, d_raw_dir, dir_capacity, d_raw_summary, d_arena, arena_floats, d_unit_dir, d_units,
+                           units_bytes, d_unit_summary, stream=None):
+        """the FITS data unit (2 x samples) of every captured run of d_raw_dir -- ro_stft_raw_units_resident.  d_raw_dir
+        [dir_capacity] (RAW_CAPTURE_DTYPE), d_raw_summary and d_arena as raw_resident leaves them; the outputs as
+        snapshot_units_resident takes them"""
+        _check(library().ro_stft_raw_units_resident(self._h, _ptr(d_raw_dir), dir_capacity, _ptr(d_raw_summary), _ptr(d_arena),
+                                                    arena_floats, _ptr(d_unit_dir), _ptr(d_units), units_bytes,
+                                                    _ptr(d_unit_summary), _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

@@ -7,6 +7,7 @@
 //   ro_stft_capi.cpp     create / destroy, the transform launches, the resident entry points
 //   ro_snapshots.cpp     the row ring and the event snapshots cut from it (ro_snapshots.hip)
 //   ro_raw.cpp           the raw I/Q of each event, cut from the resident samples (ro_raw.hip), and its host twin
+//   ro_units.cpp         the events' files as FITS data units (ro_units.hip), and their host twins
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
@@ -36,6 +37,7 @@
 #include "ro_events.h"
 #include "ro_snapshots.h"
 #include "ro_raw.h"
+#include "ro_units.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -263,6 +265,11 @@ struct ro_stft {
     // raw I/Q of the events (ro_stft_raw_resident): the plan of one call (ro_raw.h); grows with pending_capacity +
     // dir_capacity, like the block above
     DeviceBlock<char> d_raw_scratch;
+    // FITS data units (ro_stft_snapshot_units_resident, ro_stft_raw_units_resident): the plan of one call (ro_units.h);
+    // grows with dir_capacity, like the two blocks above; one block for each of the two calls (ro::UNITS_OF_IMAGES,
+    // ro::UNITS_OF_RAW), so that they do not share a plan, and the device's CU count (0: not asked for yet)
+    DeviceBlock<char> d_units_scratch[2];
+    int units_cus = 0;
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
     // belong to (one window for the consecutive call; empty: none); a handle has one precision, so one of the two sets is
