@@ -5,7 +5,7 @@
 //   ro_stream.cpp        push / flush / fetch: staging slots, captured graphs, the row sink
 //   ro_czt.cpp           lengths that are not a power of two (chirp-z on an inner handle)
 //   ro_stft_capi.cpp     create / destroy, the transform launches, the resident entry points
-//   ro_snapshots.cpp     the row ring and the event snapshots cut from it (ro_snapshots.hip)
+//   ro_snapshots.cpp     the row ring and the event snapshots cut from it (ro_snapshots.hip), and their host twin
 //   ro_raw.cpp           the raw I/Q of each event, cut from the resident samples (ro_raw.hip), and its host twin
 //   ro_units.cpp         the events' files as FITS data units (ro_units.hip), and their host twins
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
@@ -259,17 +259,18 @@ struct ro_stft {
     // their full size (ro::EVENTS_SCRATCH_BYTES, under 0.5 MiB) by the first call -- the block never grows, so no launch
     // ever has to be waited for
     DeviceBlock<char> d_events_scratch;
-    // event snapshots (ro_stft_snapshots_resident): the plan and the compacted pending lists of one call (ro_snapshots.h);
-    // grows with capacity + pending_capacity; the regrow waits for the device before the old block goes
+    // the plan-then-copy calls' scratch, each grown by grow_scratch to what a call asks for.  Event snapshots
+    // (ro_stft_snapshots_resident): the plan and the compacted pending lists of one call (ro_snapshots.h); grows with capacity
+    // + pending_capacity
     DeviceBlock<char> d_snap_scratch;
     // raw I/Q of the events (ro_stft_raw_resident): the plan of one call (ro_raw.h); grows with pending_capacity +
-    // dir_capacity, like the block above
+    // dir_capacity
     DeviceBlock<char> d_raw_scratch;
     // FITS data units (ro_stft_snapshot_units_resident, ro_stft_raw_units_resident): the plan of one call (ro_units.h);
-    // grows with dir_capacity, like the two blocks above; one block for each of the two calls (ro::UNITS_OF_IMAGES,
-    // ro::UNITS_OF_RAW), so that they do not share a plan, and the device's CU count (0: not asked for yet)
+    // grows with dir_capacity; one block for each of the two calls (ro::UNITS_OF_IMAGES, ro::UNITS_OF_RAW), so that they do
+    // not share a plan
     DeviceBlock<char> d_units_scratch[2];
-    int units_cus = 0;
+    int cus = 0;                               // the device's compute units (device_cus; 0: not asked for yet)
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
     // belong to (one window for the consecutive call; empty: none); a handle has one precision, so one of the two sets is
@@ -307,17 +308,6 @@ int tile_windows_check(const char *who, int bins, const ro_band_window_t *w, int
 // the window list and the image of a cut; rows_in / rows / row_stride are filled in by launch_tile_and_scan
 ro::CutArgs make_cut_args(const ro_band_window_t *w, int count, float *d_image, int64_t image_stride);
 
-// what ro_snapshots_host and ro_stft_snapshots_resident ask of their common arguments, as a refusal in the name of `who`;
-// d: "d_" where the arrays are the device's (the argument names of the resident call), "" on the host.  *slots: the mask's
-// highest bit + 1
-int snapshots_check(const char *who, const char *d, const ro_event_t *events, int64_t capacity,
-                    const ro_detect_summary_t *summary, uint32_t slot_mask, const int32_t *snapshot_rows,
-                    const ro_row_ring_t *ring, int64_t head_row, const ro_event_t *pending, const int64_t *pending_count,
-                    int64_t pending_capacity, const ro_snapshot_t *dir, const float *arena, int64_t arena_floats,
-                    const ro_snap_summary_t *snap_summary, int *slots);
-// ... and of a ring (null: refused too)
-int ring_check(const char *who, const ro_row_ring_t *ring);
-
 // ---- ro_stft_capi.cpp
 ro::StftArgs make_stft_args(const ro_stft *h, const void *d_iq, int64_t first_row, int64_t rows, float *d_rows,
                             int64_t row_stride, float *d_tile = nullptr, ro_scan_record_t *d_records = nullptr,
@@ -337,6 +327,13 @@ int launch_tile_and_scan(ro_stft *h, const float *d_rows, int64_t row_stride, in
                          ro_scan_record_t *d_extra = nullptr, const ro::CutArgs *cut = nullptr);
 int check_bands(const ro_stft *h, const ro_bands_t &b);
 int ensure_ln_part(ro_stft *h, int64_t rows);
+// a scratch block of the handle for a plan-then-copy call (ro_snapshots.cpp, ro_raw.cpp, ro_units.cpp), at least `need`
+// bytes; the handle's device is current.  A block that has to grow is replaced, and an earlier launch on any stream may
+// still be using the old one: the device is waited for before it goes.  A stream whose capacities stay the same allocates
+// once and never waits
+int grow_scratch(DeviceBlock<char> &block, size_t need);
+// the device's compute units, asked for once per handle: they size those calls' copy grids; the handle's device is current
+int device_cus(ro_stft *h, int *cus);
 int launch_spectra_big(ro_stft *h, const void *d_iq, int format, int64_t first_row, int64_t rows, float2 *d_out,
                        int64_t out_stride, hipStream_t s);
 

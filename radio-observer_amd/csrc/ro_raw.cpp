@@ -87,11 +87,9 @@ extern "C" int ro_stft_raw_resident(ro_stft_t *h, const ro_snapshot_t *d_dir, in
     int rate_r = 0;
     if ((rc = raw_rate(who, h->cfg.sample_rate, h->bins, h->cfg.overlap, &rate_r)) != RO_OK) return rc;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t need = ro::raw_scratch_bytes(dir_capacity, pending_capacity);
-    if (h->d_raw_scratch.count() < need) {
-        if (h->d_raw_scratch) HIP_TRY(hipDeviceSynchronize());   // (an earlier launch may still be using the old block)
-        HIP_TRY(h->d_raw_scratch.alloc(need));
-    }
+    int cus = 0;
+    if ((rc = device_cus(h, &cus)) != RO_OK) return rc;
+    if ((rc = grow_scratch(h->d_raw_scratch, ro::raw_scratch_bytes(dir_capacity, pending_capacity))) != RO_OK) return rc;
     ro::RawArgs a{};
     a.dir = d_dir;
     a.snap_summary = d_snap_summary;
@@ -117,7 +115,7 @@ extern "C" int ro_stft_raw_resident(ro_stft_t *h, const ro_snapshot_t *d_dir, in
     a.arena_floats = arena_floats;
     a.raw_summary = d_raw_summary;
     ro::raw_scratch_layout(a, h->d_raw_scratch);
-    HIP_TRY(ro::launch_raw(a, (hipStream_t)stream));
+    HIP_TRY(ro::launch_raw(a, cus, (hipStream_t)stream));
     return RO_OK;
 }
 

@@ -66,7 +66,7 @@ struct RawArgs {
 size_t raw_scratch_bytes(int64_t dir_capacity, int64_t pending_capacity);
 void raw_scratch_layout(RawArgs &a, void *scratch);
 
-// the plan and the copy on `s`: two launches
-hipError_t launch_raw(const RawArgs &a, hipStream_t s);
+// the plan and the copy on `s`: two launches; cus: the device's compute units (the copy's grid is four workgroups for each)
+hipError_t launch_raw(const RawArgs &a, int cus, hipStream_t s);
 
 }  // namespace ro

@@ -7,21 +7,17 @@
 //
 // Plain launches, as in ro_snapshots.hip; no workgroup waits for another one of its launch, no atomics, so the same input
 // gives the same bytes:
-//   raw_plan_kernel   ONE workgroup walks the candidates (the pending list, then the snapshot directory's captured entries)
-//                     RO_RAW_TILE at a time and carries three exclusive prefixes from tile to tile, all in 64 bits: the raw
-//                     directory index, the packed pairs (a run's arena offset is twice its packed pair) and the packed
-//                     blocks, besides the pending index.  It writes the raw directory, the new pending list (in place: a
-//                     kept candidate lands at or in front of where it was read, and a tile is in registers before any
-//                     of it is stored), the summary and the plan (ro_raw.h)
-//   raw_copy_kernel   a grid sized by the host from the CU count; every wave strides over the blocks (RO_RAW_BLOCK pairs
-//                     of ONE entry), finds a block's entry by binary search in the plan (the block index is wave-uniform:
-//                     no divergent loop), and converts its pairs, lanes on consecutive pairs, one pair per lane and load:
-//                     f is odd for every even hop, so a 16-byte load of two float pairs would be misaligned for almost
-//                     every event (the wider form was not measured)
-#include <algorithm>
-#include <cstddef>
-
-#include "ro_device_util.h"
+//   raw_plan_kernel   the plan of ro_pack_plan.h over the candidates (the pending list, then the snapshot directory's
+//                     captured entries): what is scanned are the packed pairs (a run's arena offset is twice its packed
+//                     pair) and, with them, the packed blocks; besides them the raw directory index and the pending index
+//                     go from tile to tile.  It writes the raw directory, the new pending list (in place: a kept
+//                     candidate lands at or in front of where it was read, and a tile is in registers before any of it is
+//                     stored), the summary and the plan (ro_raw.h)
+//   raw_copy_kernel   the copy of ro_pack_plan.h over the blocks (RO_RAW_BLOCK pairs of ONE entry): it converts a block's
+//                     pairs, lanes on consecutive pairs, one pair per lane and load: f is odd for every even hop, so a
+//                     16-byte load of two float pairs would be misaligned for almost every event (the wider form was not
+//                     measured)
+#include "ro_pack_plan.h"
 #include "ro_raw.h"
 
 namespace ro {
@@ -29,71 +25,21 @@ namespace ro {
 namespace {
 
 constexpr int T = RO_RAW_TILE;
-constexpr int WAVES = T / 64;
 constexpr int64_t B = RO_RAW_BLOCK;
-static_assert(T == 256 && WAVES == 4, "one candidate per lane, four waves");
+static_assert(T == PLAN_TILE, "one candidate per lane, four waves");
 
 enum { KIND_NONE = 0, KIND_PENDING, KIND_EMPTY, KIND_LOST, KIND_CAPTURABLE };
+constexpr unsigned RESOLVED = 0b0111u, PENDING = 0b1000u;    // of tile_count's classes: captured, empty, lost; pending
 
-// A directory entry travels as its nine 64-bit words (every ABI struct here is 8-byte aligned and has no padding).
-constexpr int EVENT_WORDS = sizeof(ro_event_t) / 8;
-constexpr int SNAP_WORDS = sizeof(ro_snapshot_t) / 8;
-static_assert(sizeof(ro_event_t) == 40 && sizeof(ro_snapshot_t) == 72 && offsetof(ro_event_t, start_row) == 8 &&
-                  offsetof(ro_snapshot_t, first_row) == 40 && offsetof(ro_snapshot_t, rows) == 56 &&
-                  offsetof(ro_snapshot_t, slot) == 60 && offsetof(ro_snapshot_t, status) == 64 &&
-                  sizeof(ro_raw_capture_t) == 72 && offsetof(ro_raw_capture_t, first_sample) == 40 &&
-                  offsetof(ro_raw_capture_t, samples) == 48 && offsetof(ro_raw_capture_t, offset) == 56 &&
-                  offsetof(ro_raw_capture_t, slot) == 64 && offsetof(ro_raw_capture_t, status) == 68,
-              "the words below are these fields");
-struct SnapWords {
-    int64_t w[SNAP_WORDS];
-    __device__ __forceinline__ int64_t start_row() const { return w[1]; }
-    __device__ __forceinline__ int64_t first_row() const { return w[5]; }
-    __device__ __forceinline__ int64_t rows() const { return (int64_t)(int32_t)(uint32_t)w[7]; }
-    __device__ __forceinline__ uint32_t slot() const { return (uint32_t)((uint64_t)w[7] >> 32); }
-    __device__ __forceinline__ int32_t status() const { return (int32_t)(uint32_t)w[8]; }
-};
-__device__ __forceinline__ SnapWords load_snapshot(const ro_snapshot_t *p)
-{
-    SnapWords e;
-    const int64_t *q = reinterpret_cast<const int64_t *>(p);
-#pragma unroll
-    for (int w = 0; w < SNAP_WORDS; ++w) e.w[w] = q[w];
-    return e;
-}
-__device__ __forceinline__ void store_snapshot(ro_snapshot_t *p, const SnapWords &e)
-{
-    int64_t *q = reinterpret_cast<int64_t *>(p);
-#pragma unroll
-    for (int w = 0; w < SNAP_WORDS; ++w) q[w] = e.w[w];
-}
-
-__device__ __forceinline__ int popc_below(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
-
-// inclusive prefix sum of a 64-bit count over the 64 lanes: four runs of wave_inclusive_sum, on 16 bits each (64 x 65535
-// fits a run with room to spare), put together modulo 2^64.  A run of up to 2^31 pairs and a tile of 256 of them need more
-// than the two runs snap_plan_kernel makes for its rows.
-__device__ __forceinline__ int64_t wave_inclusive_sum64(int64_t x)
-{
-    const uint64_t u = (uint64_t)x;
-    uint64_t sum = 0;
-#pragma unroll
-    for (int limb = 0; limb < 4; ++limb)
-        sum += (uint64_t)wave_inclusive_sum((unsigned)(u >> (16 * limb)) & 0xffffu) << (16 * limb);
-    return (int64_t)sum;
-}
-
-// One workgroup.  Per tile: every lane classifies its candidate; the pairs and the blocks of the capturable ones are
-// scanned (the waves' totals meet in LDS) -- a candidate FITS when the packed pairs up to and including its own are at most
-// arena_floats / 2, and since the scan runs over every capturable candidate, fitting or not, nothing behind the first that
-// does not fit can fit either.  What is resolved and what stays pending is known after that; both are ranked with ballots.
+// The plan.  A candidate FITS when the packed pairs up to and including its own are at most arena_floats / 2; what is
+// resolved goes to the raw directory, what stays pending to the front of the list, both in the order of the candidates.
 // (A capturable run lies inside the spans, which are real memory: the sums stay far below 2^63.)
 __global__ __launch_bounds__(T) void raw_plan_kernel(RawArgs a)
 {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    __shared__ int64_t wpairs[WAVES], wblocks[WAVES], wend_pairs[WAVES], wend_blocks[WAVES];
-    __shared__ int wcnt[4][WAVES];               // captured, empty, lost, pending of each wave
+    __shared__ int64_t wsum[2][PLAN_WAVES], wend[2][PLAN_WAVES];     // pairs, blocks
+    __shared__ int wcnt[PLAN_CLASSES][PLAN_WAVES];    // captured, empty, lost, pending of each wave
     int64_t have = *a.pending_count;             // (every lane reads it; lane 0 writes the new one at the end)
     have = have < 0 ? 0 : (have > a.pending_capacity ? a.pending_capacity : have);
     int64_t listed = a.snap_summary->resolved;
@@ -123,72 +69,32 @@ __global__ __launch_bounds__(T) void raw_plan_kernel(RawArgs a)
                        : f < a.base_sample ? KIND_LOST : KIND_CAPTURABLE;
         const int64_t pairs = kind == KIND_CAPTURABLE ? L : 0;
         const int64_t blocks = (pairs + B - 1) / B;
-        const int64_t inc_p = wave_inclusive_sum64(pairs), inc_b = wave_inclusive_sum64(blocks);
-        if (lane == 63) {
-            wpairs[wave] = inc_p;
-            wblocks[wave] = inc_b;
-        }
-        wg_sync();
-        int64_t first_p = pair_base + inc_p - pairs, first_b = block_base + inc_b - blocks, tile_p = 0, tile_b = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            if (w < wave) {
-                first_p += wpairs[w];
-                first_b += wblocks[w];
-            }
-            tile_p += wpairs[w];
-            tile_b += wblocks[w];
-        }
+        const int64_t take[2] = {pairs, blocks};
+        const TileScan<2> scan = tile_scan(take, wsum, lane, wave);
+        const int64_t first_p = pair_base + scan.before[0], first_b = block_base + scan.before[1];
         const bool fits = kind == KIND_CAPTURABLE && first_p + pairs <= arena_pairs;
         const bool pend = kind == KIND_PENDING || (kind == KIND_CAPTURABLE && !fits);
-        const unsigned long long mc = __ballot(fits), me = __ballot(kind == KIND_EMPTY), ml = __ballot(kind == KIND_LOST),
-                                 mp = __ballot(pend);
-        if (lane == 0) {
-            wcnt[0][wave] = __popcll(mc);
-            wcnt[1][wave] = __popcll(me);
-            wcnt[2][wave] = __popcll(ml);
-            wcnt[3][wave] = __popcll(mp);
-        }
-        // the captured candidates are a prefix of the capturable ones: the wave's last one ends its packed pairs and blocks
-        if (mc == 0ull ? lane == 0 : lane == 63 - __clzll((long long)mc)) {
-            wend_pairs[wave] = mc == 0ull ? 0 : first_p + pairs;
-            wend_blocks[wave] = mc == 0ull ? 0 : first_b + blocks;
-        }
-        wg_sync();
-        int res_rank = popc_below(mc | me | ml, lane), pend_rank = popc_below(mp, lane), tile_res = 0, tile_pend = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            const int res = wcnt[0][w] + wcnt[1][w] + wcnt[2][w];
-            if (w < wave) {
-                res_rank += res;
-                pend_rank += wcnt[3][w];
-            }
-            tile_res += res;
-            tile_pend += wcnt[3][w];
-            captured += wcnt[0][w];
-            empty += wcnt[1][w];
-            lost += wcnt[2][w];
-            used_pairs = wend_pairs[w] > used_pairs ? wend_pairs[w] : used_pairs;
-            used_blocks = wend_blocks[w] > used_blocks ? wend_blocks[w] : used_blocks;
-        }
+        const bool is[PLAN_CLASSES] = {fits, kind == KIND_EMPTY, kind == KIND_LOST, pend};
+        const int64_t end[2] = {first_p + pairs, first_b + blocks};
+        const TileCount<2> count = tile_count(is, end, wcnt, wend, lane, wave);
+        captured += count.total[0];
+        empty += count.total[1];
+        lost += count.total[2];
+        used_pairs = count.end[0] > used_pairs ? count.end[0] : used_pairs;
+        used_blocks = count.end[1] > used_blocks ? count.end[1] : used_blocks;
         if (fits || kind == KIND_EMPTY || kind == KIND_LOST) {
-            const int64_t d = dir_base + res_rank;
+            const int64_t d = dir_base + count.rank(RESOLVED, lane);
             const int status = fits ? RO_SNAP_CAPTURED : (kind == KIND_EMPTY ? RO_SNAP_EMPTY : RO_SNAP_LOST);
-            int64_t *out = reinterpret_cast<int64_t *>(a.raw_dir + d);     // ro_raw_capture_t, word by word
-#pragma unroll
-            for (int w = 0; w < EVENT_WORDS; ++w) out[w] = e.w[w];                         // event
-            out[EVENT_WORDS] = f;                                                          // first_sample
-            out[EVENT_WORDS + 1] = fits ? L : 0;                                           // samples
-            out[EVENT_WORDS + 2] = fits ? 2 * first_p : 0;                                 // offset
-            out[EVENT_WORDS + 3] = (int64_t)(((uint64_t)(unsigned)status << 32) | e.slot());           // slot, status
+            store_raw_capture(a.raw_dir + d, make_raw_capture(e, f, fits ? L : 0, fits ? 2 * first_p : 0, status));
             a.first_block[d] = first_b;
         }
         // (every candidate up to the end of this tile is in registers or done with: the list is compacted in place)
-        if (pend && pend_base + pend_rank < a.pending_capacity) store_snapshot(a.pending + (pend_base + pend_rank), e);
-        pair_base += tile_p;
-        block_base += tile_b;
-        dir_base += tile_res;
-        pend_base += tile_pend;
+        const int64_t pend_at = pend_base + count.rank(PENDING, lane);
+        if (pend && pend_at < a.pending_capacity) store_snapshot(a.pending + pend_at, e);
+        pair_base += scan.total[0];
+        block_base += scan.total[1];
+        dir_base += count.total[0] + count.total[1] + count.total[2];
+        pend_base += count.total[3];
     }
     if (threadIdx.x == 0) {
         const int64_t kept = pend_base < a.pending_capacity ? pend_base : a.pending_capacity;
@@ -210,7 +116,6 @@ __global__ __launch_bounds__(T) void raw_plan_kernel(RawArgs a)
     }
 }
 
-constexpr int COPY_WAVES = 4;
 constexpr int STEPS = RO_RAW_BLOCK / 64;         // loads of 64 pairs each in flight before the stores
 static_assert(STEPS * 64 == RO_RAW_BLOCK && STEPS == 8, "a block is eight pairs per lane");
 
@@ -263,10 +168,7 @@ __device__ __forceinline__ void span_pairs(const void *iq, int64_t first, int64_
     }
 }
 
-// Every wave takes blocks wave, wave + waves, ...; nothing to do when the plan's total is zero.  The entry of block b is
-// the last one whose first block is at most b: the table never descends, an entry without samples in front of a captured
-// one holds the same value and comes first, and every entry behind the last captured one holds at least the total.
-// A sample that several spans hold is read from the last: span i OWNS [first[i], first[i + 1]), the last one up to the
+// The copy: a work item is a block.  A sample that several spans hold is read from the last: span i OWNS [first[i], first[i + 1]), the last one up to the
 // head (no gap between spans, ends ascending: the owner holds the sample).  Which spans a block needs is wave-uniform, so
 // the branches below are scalar; a block inside one span runs one of them, and only a block across a boundary runs two.
 __global__ __launch_bounds__(64 * COPY_WAVES) void raw_copy_kernel(RawArgs a)
@@ -275,18 +177,12 @@ __global__ __launch_bounds__(64 * COPY_WAVES) void raw_copy_kernel(RawArgs a)
     const int64_t total = a.head->blocks;
     const int64_t resolved = a.head->resolved;
     if (total <= 0) return;
-    const unsigned waves = gridDim.x * COPY_WAVES;
-    const unsigned me = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * COPY_WAVES + (threadIdx.x >> 6)));
-    for (int64_t b = me; b < total; b += waves) {
-        int64_t lo = 0, hi = resolved;           // the first entry whose first block lies beyond b
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (a.first_block[mid] <= b) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo == 0) continue;
-        const ro_raw_capture_t *en = a.raw_dir + (lo - 1);
-        const int64_t p0 = (b - a.first_block[lo - 1]) * B;          // the block's first pair of the entry's run
+    const CopyWave wv = copy_wave();
+    for (int64_t b = wv.me; b < total; b += wv.waves) {
+        const int64_t d = plan_entry(a.first_block, resolved, b);
+        if (d < 0) continue;
+        const ro_raw_capture_t *en = a.raw_dir + d;
+        const int64_t p0 = (b - a.first_block[d]) * B;               // the block's first pair of the entry's run
         const int64_t L = en->samples, offset = en->offset;
         if (en->status != RO_SNAP_CAPTURED || p0 >= L || offset < 0 || offset + 2 * L > a.arena_floats) continue;
         const int64_t n = L - p0 < B ? L - p0 : B;                   // pairs of this block
@@ -325,7 +221,7 @@ void raw_scratch_layout(RawArgs &a, void *scratch)
     a.first_block = reinterpret_cast<int64_t *>(p + sizeof(RawPlanHead));
 }
 
-hipError_t launch_raw(const RawArgs &a, hipStream_t s)
+hipError_t launch_raw(const RawArgs &a, int cus, hipStream_t s)
 {
     if (a.dir_capacity < 0 || a.pending_capacity < 0 || a.dir_capacity + a.pending_capacity > RAW_MAX_CANDIDATES ||
         (a.dir_capacity > 0 && !a.dir) || !a.snap_summary || a.spans < 1 || a.spans > RO_MAX_IQ_SPANS || a.hop < 1 ||
@@ -340,13 +236,8 @@ hipError_t launch_raw(const RawArgs &a, hipStream_t s)
             return hipErrorInvalidValue;
     }
     if (a.base_sample != a.first[0] || a.head_sample != a.first[a.spans - 1] + a.count[a.spans - 1]) return hipErrorInvalidValue;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
     hipLaunchKernelGGL(raw_plan_kernel, dim3(1), dim3(T), 0, s, a);
-    // the work is known on the device only: four workgroups per CU, every wave strides over the blocks
-    hipLaunchKernelGGL(raw_copy_kernel, dim3((unsigned)(4 * std::max(cus, 1))), dim3(64 * COPY_WAVES), 0, s, a);
+    hipLaunchKernelGGL(raw_copy_kernel, dim3(copy_grid(cus)), dim3(64 * COPY_WAVES), 0, s, a);
     return hipGetLastError();
 }
 

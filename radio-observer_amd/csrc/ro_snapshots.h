@@ -65,7 +65,7 @@ void snap_scratch_layout(SnapArgs &a, void *scratch);
 
 // one launch on `s`
 hipError_t launch_ring_put(const RingPutArgs &a, hipStream_t s);
-// the plan and the copy on `s`: two launches
-hipError_t launch_snapshots(const SnapArgs &a, hipStream_t s);
+// the plan and the copy on `s`: two launches; cus: the device's compute units (the copy's grid is four workgroups for each)
+hipError_t launch_snapshots(const SnapArgs &a, int cus, hipStream_t s);
 
 }  // namespace ro

@@ -8,18 +8,12 @@
 // form), no atomics, so the same input gives the same bytes:
 //   ring_put_kernel   rows of an image into their ring slots: cut_windows_kernel's shape, the slot (first_row + i) %
 //                     ring_rows computed once per wave and row
-//   snap_plan_kernel  ONE workgroup walks the candidates of all slots in order, RO_SNAP_TILE at a time, and carries three
-//                     exclusive prefixes from tile to tile: the directory index, the packed rows (int64; an image's arena
-//                     offset is its packed row x cols) and the slot's pending index.  It writes the directory, the new
-//                     pending lists, the summary and the plan (ro_snapshots.h) -- the candidates are few, nobody waits for
-//                     this kernel, and one workgroup needs no ordering between workgroups
-//   snap_copy_kernel  a grid sized by the host from the CU count; every wave strides over the packed rows, finds a row's
-//                     directory entry by binary search in the plan (the row index is wave-uniform: scalar loads, no
-//                     divergent loop) and copies its cols floats from the ring slot to the arena
-#include <algorithm>
-#include <cstddef>
-
-#include "ro_device_util.h"
+//   snap_plan_kernel  the plan of ro_pack_plan.h over the candidates of all slots in order: what is scanned are the packed
+//                     rows (an image's arena offset is its packed row x cols); besides them the directory index and the
+//                     slot's pending index go from tile to tile.  It writes the directory, the new pending lists, the
+//                     summary and the plan (ro_snapshots.h)
+//   snap_copy_kernel  the copy of ro_pack_plan.h over the packed rows: a row's cols floats from the ring slot to the arena
+#include "ro_pack_plan.h"
 #include "ro_snapshots.h"
 
 namespace ro {
@@ -27,8 +21,7 @@ namespace ro {
 namespace {
 
 constexpr int T = RO_SNAP_TILE;
-constexpr int WAVES = T / 64;
-static_assert(T == 256 && WAVES == 4, "one candidate per lane, four waves");
+static_assert(T == PLAN_TILE, "one candidate per lane, four waves");
 
 constexpr int PUT_WAVES = 4;                    // waves of a workgroup, each on rows of its own
 constexpr int PUT_STEPS = 4;                    // runs of 64 columns per wave: a workgroup spans 256 columns ...
@@ -72,48 +65,16 @@ __global__ __launch_bounds__(64 * PUT_WAVES) void ring_put_kernel(RingPutArgs a,
 }
 
 enum { KIND_NONE = 0, KIND_PENDING, KIND_EMPTY, KIND_LOST, KIND_CAPTURABLE };
+constexpr unsigned RESOLVED = 0b0111u, PENDING = 0b1000u;    // of tile_count's classes: captured, empty, lost; pending
 
-// An event travels as its five 64-bit words (every ABI struct here is 8-byte aligned and has no padding): copied field by
-// field, its float / int tail went through a private array.
-constexpr int EVENT_WORDS = sizeof(ro_event_t) / 8;
-static_assert(sizeof(ro_event_t) == 40 && sizeof(ro_snapshot_t) == 72 && offsetof(ro_event_t, start_row) == 8 &&
-                  offsetof(ro_event_t, length) == 16 && offsetof(ro_snapshot_t, first_row) == 40 &&
-                  offsetof(ro_snapshot_t, offset) == 48 && offsetof(ro_snapshot_t, rows) == 56 &&
-                  offsetof(ro_snapshot_t, slot) == 60 && offsetof(ro_snapshot_t, status) == 64,
-              "the words below are these fields");
-struct EventWords {
-    int64_t w[EVENT_WORDS];
-    __device__ __forceinline__ int64_t start_row() const { return w[1]; }
-    __device__ __forceinline__ int64_t length() const { return w[2]; }
-};
-__device__ __forceinline__ EventWords load_event(const ro_event_t *p)
-{
-    EventWords e;
-    const int64_t *q = reinterpret_cast<const int64_t *>(p);
-#pragma unroll
-    for (int w = 0; w < EVENT_WORDS; ++w) e.w[w] = q[w];
-    return e;
-}
-__device__ __forceinline__ void store_event(ro_event_t *p, const EventWords &e)
-{
-    int64_t *q = reinterpret_cast<int64_t *>(p);
-#pragma unroll
-    for (int w = 0; w < EVENT_WORDS; ++w) q[w] = e.w[w];
-}
-
-__device__ __forceinline__ int popc_below(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
-
-// One workgroup.  Per tile: every lane classifies its candidate; the rows of the capturable ones are scanned (two runs of
-// wave_inclusive_sum, on the low 16 bits and on the rest of a count below 2^31, put together as int64; the waves' totals
-// meet in LDS) -- a candidate FITS when the packed rows up to and including its own are at most arena_rows, and since the
-// scan runs over every capturable candidate, fitting or not, nothing behind the first that does not fit can fit either.
-// What is resolved and what stays pending is known after that; both are ranked with ballots.
+// The plan.  A candidate FITS when the packed rows up to and including its own are at most arena_rows; what is resolved
+// goes to the directory, what stays pending to the slot's new list, both in the order of the candidates.
 __global__ __launch_bounds__(T) void snap_plan_kernel(SnapArgs a)
 {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    __shared__ int64_t wrows[WAVES], wend[WAVES];
-    __shared__ int wcnt[4][WAVES];               // captured, empty, lost, pending of each wave
+    __shared__ int64_t wrows[1][PLAN_WAVES], wend[1][PLAN_WAVES];
+    __shared__ int wcnt[PLAN_CLASSES][PLAN_WAVES];    // captured, empty, lost, pending of each wave
     int64_t row_base = 0;                        // packed rows of the capturable candidates in front of the tile
     int64_t packed_rows = 0;                     // ... of the captured ones: where the last captured image ends
     int dir_base = 0;
@@ -148,61 +109,29 @@ __global__ __launch_bounds__(T) void snap_plan_kernel(SnapArgs a)
                            : hi <= lo ? KIND_EMPTY
                            : lo < a.head_row - a.ring_rows ? KIND_LOST : KIND_CAPTURABLE;
             const int rows = kind == KIND_CAPTURABLE ? (int)(hi - lo) : 0;   // 1 ... snap
-            const unsigned inc_lo = wave_inclusive_sum((unsigned)rows & 0xffffu);
-            const unsigned inc_hi = wave_inclusive_sum((unsigned)rows >> 16);
-            const int64_t inc = ((int64_t)inc_hi << 16) + (int64_t)inc_lo;
-            if (lane == 63) wrows[wave] = inc;
-            wg_sync();
-            int64_t first = row_base + inc - rows, tile_rows = 0;          // packed row where this candidate's image starts
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) {
-                if (w < wave) first += wrows[w];
-                tile_rows += wrows[w];
-            }
+            const int64_t take[1] = {rows};
+            const TileScan<1> scan = tile_scan(take, wrows, lane, wave);
+            const int64_t first = row_base + scan.before[0];                 // packed row where this candidate's image starts
             const bool fits = kind == KIND_CAPTURABLE && first + rows <= a.arena_rows;
             const bool pend = kind == KIND_PENDING || (kind == KIND_CAPTURABLE && !fits);
-            const unsigned long long mc = __ballot(fits), me = __ballot(kind == KIND_EMPTY), ml = __ballot(kind == KIND_LOST),
-                                     mp = __ballot(pend);
-            if (lane == 0) {
-                wcnt[0][wave] = __popcll(mc);
-                wcnt[1][wave] = __popcll(me);
-                wcnt[2][wave] = __popcll(ml);
-                wcnt[3][wave] = __popcll(mp);
-            }
-            // the captured candidates are a prefix of the capturable ones: the wave's last one ends its packed rows
-            if (mc == 0ull ? lane == 0 : lane == 63 - __clzll((long long)mc)) wend[wave] = mc == 0ull ? 0 : first + rows;
-            wg_sync();
-            int res_rank = popc_below(mc | me | ml, lane), pend_rank = popc_below(mp, lane), tile_res = 0, tile_pend = 0;
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) {
-                const int res = wcnt[0][w] + wcnt[1][w] + wcnt[2][w];
-                if (w < wave) {
-                    res_rank += res;
-                    pend_rank += wcnt[3][w];
-                }
-                tile_res += res;
-                tile_pend += wcnt[3][w];
-                captured += wcnt[0][w];
-                empty += wcnt[1][w];
-                lost += wcnt[2][w];
-                packed_rows = wend[w] > packed_rows ? wend[w] : packed_rows;
-            }
+            const bool is[PLAN_CLASSES] = {fits, kind == KIND_EMPTY, kind == KIND_LOST, pend};
+            const int64_t end[1] = {first + rows};
+            const TileCount<1> count = tile_count(is, end, wcnt, wend, lane, wave);
+            captured += count.total[0];
+            empty += count.total[1];
+            lost += count.total[2];
+            packed_rows = count.end[0] > packed_rows ? count.end[0] : packed_rows;
             if (fits || kind == KIND_EMPTY || kind == KIND_LOST) {
-                const int d = dir_base + res_rank;
+                const int d = dir_base + count.rank(RESOLVED, lane);
                 const int status = fits ? RO_SNAP_CAPTURED : (kind == KIND_EMPTY ? RO_SNAP_EMPTY : RO_SNAP_LOST);
-                int64_t *out = reinterpret_cast<int64_t *>(a.dir + d);       // ro_snapshot_t, word by word
-#pragma unroll
-                for (int w = 0; w < EVENT_WORDS; ++w) out[w] = e.w[w];                       // event
-                out[EVENT_WORDS] = lo;                                                       // first_row
-                out[EVENT_WORDS + 1] = fits ? first * a.cols : 0;                            // offset
-                out[EVENT_WORDS + 2] = (int64_t)(((uint64_t)(unsigned)s << 32) | (unsigned)(fits ? rows : 0));    // rows, slot
-                out[EVENT_WORDS + 3] = (int64_t)(unsigned)status;                            // status, reserved = 0
+                store_snapshot(a.dir + d, make_snapshot(e, lo, fits ? first * a.cols : 0, fits ? rows : 0, s, status));
                 a.first_packed[d] = first;
             }
-            if (pend && pend_base + pend_rank < a.pending_capacity) store_event(new_list + (pend_base + pend_rank), e);
-            row_base += tile_rows;
-            dir_base += tile_res;
-            pend_base += tile_pend;
+            const int64_t pend_at = pend_base + count.rank(PENDING, lane);
+            if (pend && pend_at < a.pending_capacity) store_event(new_list + pend_at, e);
+            row_base += scan.total[0];
+            dir_base += count.total[0] + count.total[1] + count.total[2];
+            pend_base += count.total[3];
         }
         // the slot's new list is complete in scratch, and nobody reads the old one any more: it goes back
         __threadfence_block();
@@ -231,31 +160,21 @@ __global__ __launch_bounds__(T) void snap_plan_kernel(SnapArgs a)
     }
 }
 
-constexpr int COPY_WAVES = 4;
 constexpr int COPY_STEPS = 4;                   // loads of 64 columns each in flight before the stores
 
-// Every wave takes packed rows wave, wave + waves, ...; nothing to do when the plan's total is zero.  The entry of packed
-// row p is the last one whose first packed row is at most p: the table never descends, an entry without rows in front of
-// a captured one holds the same value and comes first, and every entry behind the last captured one holds at least the
-// total.
+// The copy: a work item is a packed row.
 __global__ __launch_bounds__(64 * COPY_WAVES) void snap_copy_kernel(SnapArgs a)
 {
     const int lane = threadIdx.x & 63;
     const int64_t total = a.head->packed_rows;
     const int64_t resolved = a.head->resolved;
     if (total <= 0) return;
-    const unsigned waves = gridDim.x * COPY_WAVES;
-    const unsigned me = (unsigned)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * COPY_WAVES + (threadIdx.x >> 6)));
-    for (int64_t p = me; p < total; p += waves) {
-        int64_t lo = 0, hi = resolved;           // the first entry whose first packed row lies beyond p
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (a.first_packed[mid] <= p) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo == 0) continue;
-        const ro_snapshot_t *en = a.dir + (lo - 1);
-        const int64_t k = p - a.first_packed[lo - 1];
+    const CopyWave wv = copy_wave();
+    for (int64_t p = wv.me; p < total; p += wv.waves) {
+        const int64_t d = plan_entry(a.first_packed, resolved, p);
+        if (d < 0) continue;
+        const ro_snapshot_t *en = a.dir + d;
+        const int64_t k = p - a.first_packed[d];
         const int64_t offset = en->offset + k * a.cols;
         if (en->status != RO_SNAP_CAPTURED || k >= en->rows || offset + a.cols > a.arena_floats) continue;
         const float *in = a.ring + ((en->first_row + k) % a.ring_rows) * a.ring_stride;
@@ -305,7 +224,7 @@ hipError_t launch_ring_put(const RingPutArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_snapshots(const SnapArgs &a, hipStream_t s)
+hipError_t launch_snapshots(const SnapArgs &a, int cus, hipStream_t s)
 {
     if (a.slots < 1 || a.slots > SNAP_MAX_SLOTS || a.slot_mask == 0u || (a.slot_mask >> a.slots) != 0u || a.capacity < 0 ||
         a.pending_capacity < 0 || (a.capacity > 0 && (!a.events || !a.summary)) || !a.ring || a.ring_rows < 1 || a.cols < 1 ||
@@ -314,13 +233,8 @@ hipError_t launch_snapshots(const SnapArgs &a, hipStream_t s)
         !a.head || !a.first_packed || !a.pending_new ||
         (int64_t)a.slots * (a.capacity + a.pending_capacity) > SNAP_MAX_SLOTS * SNAP_MAX_CANDIDATES)
         return hipErrorInvalidValue;
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
     hipLaunchKernelGGL(snap_plan_kernel, dim3(1), dim3(T), 0, s, a);
-    // the work is known on the device only: four workgroups per CU, every wave strides over the packed rows
-    hipLaunchKernelGGL(snap_copy_kernel, dim3((unsigned)(4 * std::max(cus, 1))), dim3(64 * COPY_WAVES), 0, s, a);
+    hipLaunchKernelGGL(snap_copy_kernel, dim3(copy_grid(cus)), dim3(64 * COPY_WAVES), 0, s, a);
     return hipGetLastError();
 }
 

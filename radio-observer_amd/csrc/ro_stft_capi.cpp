@@ -343,6 +343,21 @@ int ensure_ln_part(ro_stft *h, int64_t rows)
     return RO_OK;
 }
 
+int grow_scratch(DeviceBlock<char> &block, size_t need)
+{
+    if (block.count() >= need) return RO_OK;
+    if (block) HIP_TRY(hipDeviceSynchronize());                   // (an earlier launch may still be using the old block)
+    HIP_TRY(block.alloc(need));
+    return RO_OK;
+}
+
+int device_cus(ro_stft *h, int *cus)
+{
+    if (h->cus == 0) HIP_TRY(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    *cus = h->cus;
+    return RO_OK;
+}
+
 // complex spectra of rows [first_row, +rows) of a large size (bins = dec x 32768), bin k at element k of each row:
 // fold_kernel, the N = 32768 kernel in spectra mode on its rows, interleave2_kernel
 int launch_spectra_big(ro_stft *h, const void *d_iq, int format, int64_t first_row, int64_t rows, float2 *d_out,

@@ -55,16 +55,12 @@ int units_check(const char *who, const char *d, bool raw, bool aligned, const vo
 int units_launch(ro_stft_t *h, ro::UnitsArgs &a, int kind, void *stream)
 {
     HIP_TRY(hipSetDevice(h->device));
-    if (h->units_cus == 0) HIP_TRY(hipDeviceGetAttribute(&h->units_cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    int cus = 0, rc = device_cus(h, &cus);
+    if (rc != RO_OK) return rc;
     // one block per kind: the images' call and the raw runs' call of a chunk may be in flight on two streams
-    ro_stft::DeviceBlock<char> &scratch = h->d_units_scratch[kind];
-    const size_t need = ro::units_scratch_bytes(a.dir_capacity);
-    if (scratch.count() < need) {
-        if (scratch) HIP_TRY(hipDeviceSynchronize());             // (an earlier launch may still be using the old block)
-        HIP_TRY(scratch.alloc(need));
-    }
-    ro::units_scratch_layout(a, scratch);
-    HIP_TRY(ro::launch_units(a, kind, h->units_cus, (hipStream_t)stream));
+    if ((rc = grow_scratch(h->d_units_scratch[kind], ro::units_scratch_bytes(a.dir_capacity))) != RO_OK) return rc;
+    ro::units_scratch_layout(a, h->d_units_scratch[kind]);
+    HIP_TRY(ro::launch_units(a, kind, cus, (hipStream_t)stream));
     return RO_OK;
 }
 
