@@ -776,8 +776,8 @@ typedef struct ro_unit_summary {   /* 64 bytes, overwritten by every call */
  * the status.  A written unit: float i = r naxis1 + c is arena float offset + r cols + first_col + c with its four bytes
  * reversed -- a bit copy: NaN payloads, -0 and denormals survive -- and the bytes from `bytes` to the end of the last
  * block are zero.  Bytes of d_units past the summary's units_bytes are not touched.  Nothing is remembered and the sources
- * are not written: a call can be repeated with a larger d_units, and a directory built by hand over any packed image gives
- * the periodic SnapshotRecorder the same service.  n == 0 is RO_OK with a zero summary.
+ * are not written: a call can be repeated with a larger d_units.  (The periodic SnapshotRecorder has a call of its own,
+ * ro_stft_periodic_units_resident below, from the ring straight to the units.)  n == 0 is RO_OK with a zero summary.
  * RO_ERR_INVALID, before anything is launched, the text naming the argument: a null handle, d_snap_summary, slot_windows,
  * d_unit_dir or d_unit_summary; d_dir == NULL with dir_capacity > 0; d_arena == NULL with arena_floats > 0; d_units == NULL
  * with units_bytes > 0; d_units not aligned to 16 bytes; a negative dir_capacity, arena_floats or units_bytes; dir_capacity >
@@ -811,6 +811,105 @@ int ro_snapshot_units_host(const ro_snapshot_t *dir, int64_t dir_capacity, const
 int ro_raw_units_host(const ro_raw_capture_t *raw_dir, int64_t dir_capacity, const ro_raw_summary_t *raw_summary,
                       const float *arena, int64_t arena_floats,
                       ro_fits_unit_t *unit_dir, void *units, int64_t units_bytes, ro_unit_summary_t *unit_summary);
+
+/* ---- periodic snapshots: FITS data units cut from the row ring ---------------------
+ * The recorder that is always on: the "snapshot" SnapshotRecorder of both station configurations writes [leftBin, rightBin)
+ * of EVERY row into a file each snapshot_length seconds (src/WaterfallBackend.cpp:415-427, :107-127, :141-211).  Its cadence
+ * has a closed form, every size is known on the host, and so the plan is host arithmetic and ONE launch goes from the
+ * ring's slots to the big-endian, padded data units: no packed image, no directory on the device.
+ * With mark = row + 1 and S = snapshotRows_ >= 1: snapshot k >= 0 is rows [k S, (k + 1) S).  update() queues it when
+ * size(start) >= snapshotRows_ + 2 (:417), that is at row (k + 1) S + 1; startWriting() clamps the length to S (:113-115) and
+ * the next snapshot starts at its end (:122-123).  With head_row = H (rows [0, H) have been seen) snapshot k is DUE iff
+ * (k + 1) S + 2 <= H.  stop() (:400-403, writeUnfinished_) queues one more: [k' S, min((k' + 1) S, H)) for the first k' that
+ * is not due -- the `final` one.
+ * Two deviations: a final snapshot WITHOUT rows makes no entry (the reference's RingBuffer2D::size returns the ring's
+ * capacity for an empty range and would write S stale rows); and a snapshot whose rows the ring no longer holds is LOST,
+ * where the reference's reservation would have blocked the writer (as for the event snapshots above). */
+#define RO_MAX_PERIODIC 8
+enum { RO_PERIODIC_WRITTEN = 0, RO_PERIODIC_LOST = 1, RO_PERIODIC_NO_ROOM = 2 };
+
+typedef struct ro_periodic {       /* 12 bytes: one periodic recorder */
+    int32_t          snapshot_rows;            /* S >= 1: ro_snapshot_rows */
+    ro_band_window_t window;                   /* its [leftBin, rightBin) in RING columns: cols >= 1, inside the ring's cols */
+} ro_periodic_t;
+
+typedef struct ro_periodic_entry { /* 56 bytes: one snapshot of one recorder */
+    int64_t index;                 /* k */
+    int64_t first_row;             /* k S */
+    int64_t due_row;               /* the row whose update() queues it: (k + 1) S + 1; H - 1 for the final one */
+    int64_t offset;                /* bytes into the units, a multiple of 2880; 0 unless WRITTEN */
+    int64_t bytes;                 /* 4 naxis1 rows: the data; the unit occupies this rounded up to 2880.  0 if LOST */
+    int32_t rows;                  /* naxis2: S, or what the final one has, 1 ... S */
+    int32_t naxis1;                /* the window's cols */
+    int32_t recorder;
+    int32_t status;                /* RO_PERIODIC_* */
+} ro_periodic_entry_t;
+
+typedef struct ro_periodic_summary {           /* 64 bytes, overwritten by every call */
+    int64_t entries, written, lost, no_room;
+    int64_t unlisted;              /* candidates beyond `capacity`: not listed, not advanced */
+    int64_t units_bytes;           /* end of the last WRITTEN unit */
+    int64_t needed_bytes;          /* 2880 * the blocks of ALL listed writable entries: the room that holds them */
+    int64_t reserved;              /* 0 */
+} ro_periodic_summary_t;
+
+/* snapshotRows_ of a recorder: (int)ceil(snapshot_length * fft rate) with the float rate of ro_fft_sample_rate, at least 1
+ * (SnapshotRecorder::requestBufferSize, src/WaterfallBackend.cpp:339-345; the ring it asks for is 8 times that). */
+int ro_snapshot_rows(int sample_rate, int bins, int overlap, int snapshot_length);
+
+/* The plan of one call: pure host arithmetic, no handle, no device.
+ *   recorders, count   1 ... RO_MAX_PERIODIC recorders; windows in columns of a ring row of `cols` floats
+ *   next_index         host, [count], in / out, zero-filled once: the first snapshot of each recorder that is not resolved
+ *   head_row, final    H >= 0: rows [0, H) are in the stream, and the ring holds [max(0, H - ring_rows), H); final != 0: stop()
+ *   ring_rows, cols    of the ring the units will be cut from
+ *   units_bytes        room of the units buffer
+ *   dir, capacity      room for `capacity` entries (NULL with 0); entries behind the summary's `entries` are not touched
+ * A recorder's CANDIDATES are its due snapshots k = next_index, next_index + 1, ... and, with `final`, the final one if it
+ * has rows (a next_index beyond the first snapshot that is not due says that the final one has resolved already: none);
+ * recorders in ascending order.  For each, in this order:
+ *   1  first_row < H - ring_rows      RO_PERIODIC_LOST: it resolves, nothing is written; it carries rows and naxis1
+ *   2  otherwise                      WRITABLE with blocks = ceil(4 naxis1 rows / 2880)
+ * `offset` is 2880 x the exclusive prefix sum of `blocks` over the writable candidates.  A writable candidate with offset +
+ * 2880 blocks <= units_bytes is RO_PERIODIC_WRITTEN; the first that does not fit and every writable one behind it, of any
+ * recorder, is RO_PERIODIC_NO_ROOM: it has its shape and offset 0, is not resolved and comes back in the next call.  A
+ * recorder's next_index advances past its LEADING resolved entries only.  Candidates beyond `capacity` are not listed and
+ * not advanced; the summary counts them.  Called with any sequence of non-decreasing head_row, repeats included, the plan
+ * yields each snapshot exactly once in total.  The host knows due_row from here: the 12-byte scan record behind a
+ * snapshot's listenToNoise_ CSV line (:157-167) is a copy the host issues itself.
+ * RO_ERR_INVALID, the text naming the argument: null recorders, next_index or summary; dir == NULL with capacity > 0; count
+ * outside 1 ... RO_MAX_PERIODIC; snapshot_rows < 1; a window with first_col < 0, cols < 1 or first_col + cols > cols; a
+ * negative head_row, units_bytes, capacity or next_index entry (or rows beyond 2^62); ring_rows < 1; cols < 1. */
+int ro_periodic_plan(const ro_periodic_t *recorders, int count, int64_t *next_index, int64_t head_row, int final,
+                     int64_t ring_rows, int32_t cols, int64_t units_bytes,
+                     ro_periodic_entry_t *dir, int64_t capacity, ro_periodic_summary_t *summary);
+
+/* The units of one plan: ONE plain launch (csrc/ro_periodic.hip), ring -> units.  dir is HOST memory, as ro_periodic_plan
+ * left it, `entries` of them; nothing but scalars reaches the kernel (per recorder its first written snapshot, how many, S,
+ * the window, the blocks of a unit and where the first one starts: all in the kernel arguments).  No directory upload, no
+ * plan kernel, no handle scratch.  A written unit: float i = r naxis1 + c is ring float
+ * ((first_row + r) % ring_rows) stride + first_col + c with its four bytes reversed -- a bit copy -- and the bytes from
+ * `bytes` to the end of the last block are zero.  The ring is only read; bytes of d_units behind the last written unit are
+ * not touched; no atomics: equal inputs give equal bytes.  Asynchronous on `stream`: issue it behind
+ * ro_stft_ring_put_resident on the same stream, with the head_row the plan was given in the ring.  entries == 0, or none
+ * WRITTEN, launches nothing.
+ * RO_ERR_INVALID, before anything is launched, the text naming the argument: a null handle, ring, ring->d_rows, recorders or
+ * dir (entries > 0); a ring as ro_stft_ring_put_resident refuses it; count outside 1 ... RO_MAX_PERIODIC; snapshot_rows <
+ * 1; a window with first_col < 0, cols < 1 or first_col + cols > ring->cols; a negative entries or units_bytes; d_units ==
+ * NULL with units_bytes > 0, or not aligned to 16 bytes; [d_units, + units_bytes) overlapping the ring; a directory that is
+ * not what the plan writes for these recorders: recorders ascending, a recorder's indices consecutive, first_row = index x
+ * S, rows = S but for a recorder's last entry (1 ... S), rows <= ring_rows, naxis1 and bytes those of the window, an
+ * unknown status, a WRITTEN entry behind a NO_ROOM one, and the WRITTEN entries' offsets the multiples of 2880 that pack
+ * them from 0 on, inside units_bytes.
+ * The older route keeps working: un-wrap the ring into a packed image, build ro_snapshot_t entries by hand, then
+ * ro_stft_snapshot_units_resident. */
+int ro_stft_periodic_units_resident(ro_stft_t *h, const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count,
+                                    const ro_periodic_entry_t *dir, int64_t entries, void *d_units, int64_t units_bytes,
+                                    void *stream);
+
+/* The same rules over host memory, ring->d_rows included: no handle, no device.  The yardstick of the device call: equal
+ * inputs give equal bytes.  Refusals as above, without the handle and the alignment. */
+int ro_periodic_units_host(const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count,
+                           const ro_periodic_entry_t *dir, int64_t entries, void *units, int64_t units_bytes);
 
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel

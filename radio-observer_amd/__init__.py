@@ -23,6 +23,8 @@ from .capi import (  # noqa: F401
     raw_host, IqSpan, RAW_CAPTURE_DTYPE, RAW_SUMMARY_DTYPE, RO_MAX_IQ_SPANS,
     snapshot_units_host, raw_units_host, FITS_UNIT_DTYPE, UNIT_SUMMARY_DTYPE, RO_FITS_BLOCK,
     RO_UNIT_WRITTEN, RO_UNIT_SKIPPED, RO_UNIT_NO_ROOM, RO_UNIT_INVALID,
+    snapshot_rows, periodic_plan, periodic_units_host, periodic_recorders, PERIODIC_DTYPE, PERIODIC_ENTRY_DTYPE,
+    PERIODIC_SUMMARY_DTYPE, RO_MAX_PERIODIC, RO_PERIODIC_WRITTEN, RO_PERIODIC_LOST, RO_PERIODIC_NO_ROOM,
     RO_WINDOW_NUTTALL, RO_WINDOW_HANN, RO_WINDOW_CUSTOM, RO_IQ_F32, RO_IQ_I16, RO_IQ_F64,
     RO_PRECISION_F32, RO_PRECISION_F64,
 )

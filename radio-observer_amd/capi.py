@@ -118,6 +118,18 @@ UNIT_SUMMARY_DTYPE = np.dtype([("entries", np.int64), ("written", np.int64), ("s
                                ("invalid", np.int64), ("units_bytes", np.int64), ("needed_bytes", np.int64),
                                ("reserved", np.int64)])
 
+RO_MAX_PERIODIC = 8
+RO_PERIODIC_WRITTEN, RO_PERIODIC_LOST, RO_PERIODIC_NO_ROOM = 0, 1, 2
+# ro_periodic_t (12 bytes: one periodic recorder), ro_periodic_entry_t (56: one snapshot of one recorder) and
+# ro_periodic_summary_t (64, one per plan)
+PERIODIC_DTYPE = np.dtype([("snapshot_rows", np.int32), ("first_col", np.int32), ("cols", np.int32)])
+PERIODIC_ENTRY_DTYPE = np.dtype([("index", np.int64), ("first_row", np.int64), ("due_row", np.int64), ("offset", np.int64),
+                                 ("bytes", np.int64), ("rows", np.int32), ("naxis1", np.int32), ("recorder", np.int32),
+                                 ("status", np.int32)])
+PERIODIC_SUMMARY_DTYPE = np.dtype([("entries", np.int64), ("written", np.int64), ("lost", np.int64), ("no_room", np.int64),
+                                   ("unlisted", np.int64), ("units_bytes", np.int64), ("needed_bytes", np.int64),
+                                   ("reserved", np.int64)])
+
 
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bins", C.c_int32), ("overlap", C.c_int32),
@@ -235,6 +247,12 @@ _EXPORTS = {
                                          C.POINTER(BandWindow), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ro_raw_units_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_void_p]),
+    "ro_snapshot_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ro_periodic_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int32, C.c_int64,
+                                   C.c_void_p, C.c_int64, C.c_void_p]),
+    "ro_stft_periodic_units_resident": (C.c_int, [C.c_void_p, C.POINTER(RowRing), C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "ro_periodic_units_host": (C.c_int, [C.POINTER(RowRing), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -635,6 +653,59 @@ def raw_units_host(raw_directory, raw_summary, arena, units_bytes):
     return _units_host(library().ro_raw_units_host, raw_directory, RAW_CAPTURE_DTYPE, raw_summary, arena, units_bytes)
 
 
+def snapshot_rows(sample_rate, bins, overlap, snapshot_length):
+    """snapshotRows_ of a periodic recorder -- ro_snapshot_rows (src/WaterfallBackend.cpp:339-345)"""
+    return library().ro_snapshot_rows(sample_rate, bins, overlap, snapshot_length)
+
+
+def periodic_recorders(recorders):
+    """a PERIODIC_DTYPE array, or (snapshot_rows, first_col, cols) per recorder -> a C-contiguous PERIODIC_DTYPE array"""
+    if isinstance(recorders, np.ndarray) and recorders.dtype == PERIODIC_DTYPE:
+        return np.ascontiguousarray(recorders)
+    out = np.zeros(len(recorders), PERIODIC_DTYPE)
+    for i, r in enumerate(recorders):
+        out[i] = tuple(int(x) for x in r)
+    return out
+
+
+def periodic_plan(recorders, next_index, head_row, final, ring_rows, cols, units_bytes, capacity):
+    """What the periodic recorders have to write at head_row -- ro_periodic_plan, pure host arithmetic.  recorders: see
+    periodic_recorders; next_index: int64 [count], zero-filled once, updated in place.  Returns (directory, summary): the
+    PERIODIC_ENTRY_DTYPE entries listed and a PERIODIC_SUMMARY_DTYPE scalar."""
+    recs = periodic_recorders(recorders)
+    if not isinstance(next_index, np.ndarray) or next_index.dtype != np.int64 or next_index.ndim != 1 or \
+            next_index.shape[0] < len(recs) or not next_index.flags.c_contiguous:
+        raise ValueError("next_index: a C-contiguous int64 array [count]")
+    directory = np.zeros(max(capacity, 1), PERIODIC_ENTRY_DTYPE)
+    out = np.zeros(1, PERIODIC_SUMMARY_DTYPE)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_periodic_plan(p(recs) if len(recs) else None, len(recs), p(next_index), head_row, 1 if final else 0,
+                                      ring_rows, cols, units_bytes, p(directory) if capacity > 0 else None, capacity, p(out)))
+    return directory[:int(out["entries"][0])], out[0]
+
+
+def periodic_units_host(ring, recorders, directory, units_bytes, cols=None):
+    """The FITS data units of one plan over host memory -- ro_periodic_units_host.  ring: float32 [ring_rows, stride], stream
+    row r in ring[r % ring_rows], `cols` floats of it (None: stride); directory: PERIODIC_ENTRY_DTYPE entries as
+    periodic_plan returned them.  Returns the bytes of the units in use."""
+    ring = np.asarray(ring)
+    if ring.dtype != np.float32 or ring.ndim != 2 or not ring.flags.c_contiguous:
+        raise ValueError("ring: a C-contiguous float32 array [ring_rows, stride]")
+    desc = RowRing(ring.ctypes.data, ring.shape[1], ring.shape[0], ring.shape[1] if cols is None else cols, 0)
+    recs = periodic_recorders(recorders)
+    directory = np.ascontiguousarray(directory)
+    if directory.dtype != PERIODIC_ENTRY_DTYPE or directory.ndim != 1:
+        raise ValueError("directory: PERIODIC_ENTRY_DTYPE [entries]")
+    units = np.zeros(max(units_bytes, 1), np.uint8)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_periodic_units_host(C.byref(desc), p(recs) if len(recs) else None, len(recs),
+                                            p(directory) if len(directory) else None, len(directory),
+                                            p(units) if units_bytes > 0 else None, units_bytes))
+    written = directory[directory["status"] == RO_PERIODIC_WRITTEN]
+    used = 0 if not len(written) else int(written[-1]["offset"]) + -(-int(written[-1]["bytes"]) // RO_FITS_BLOCK) * RO_FITS_BLOCK
+    return units[:used]
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -832,6 +903,21 @@ class Stft:
         _check(library().ro_stft_raw_units_resident(self._h, _ptr(d_raw_dir), dir_capacity, _ptr(d_raw_summary), _ptr(d_arena),
                                                     arena_floats, _ptr(d_unit_dir), _ptr(d_units), units_bytes,
                                                     _ptr(d_unit_summary), _ptr(stream)))
+
+    def periodic_units_resident(self, ring, recorders, directory, d_units, units_bytes, stream=None):
+        """the FITS data unit of every WRITTEN entry of `directory`, cut from the ring's slots to its recorder's columns,
+        big-endian, zero-padded to 2880 bytes, at the entry's offset of d_units: one launch --
+        ro_stft_periodic_units_resident.  ring: RowRing; recorders and directory (HOST, PERIODIC_ENTRY_DTYPE) as
+        periodic_plan took and returned them; d_units: units_bytes bytes, aligned to 16.  Issue it behind ring_put_resident
+        on the same stream"""
+        recs = periodic_recorders(recorders)
+        directory = np.ascontiguousarray(directory)
+        if directory.dtype != PERIODIC_ENTRY_DTYPE or directory.ndim != 1:
+            raise ValueError("directory: PERIODIC_ENTRY_DTYPE [entries]")
+        p = lambda a: C.c_void_p(a.ctypes.data)
+        _check(library().ro_stft_periodic_units_resident(self._h, C.byref(ring), p(recs) if len(recs) else None, len(recs),
+                                                         p(directory) if len(directory) else None, len(directory),
+                                                         _ptr(d_units), units_bytes, _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

@@ -8,6 +8,8 @@
 //   ro_snapshots.cpp     the row ring and the event snapshots cut from it (ro_snapshots.hip), and their host twin
 //   ro_raw.cpp           the raw I/Q of each event, cut from the resident samples (ro_raw.hip), and its host twin
 //   ro_units.cpp         the events' files as FITS data units (ro_units.hip), and their host twins
+//   ro_periodic.cpp      the periodic snapshots' plan (host arithmetic), their data units cut from the ring (ro_periodic.hip)
+//                        and the host twin
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
@@ -38,6 +40,7 @@
 #include "ro_snapshots.h"
 #include "ro_raw.h"
 #include "ro_units.h"
+#include "ro_periodic.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -336,6 +339,10 @@ int grow_scratch(DeviceBlock<char> &block, size_t need);
 int device_cus(ro_stft *h, int *cus);
 int launch_spectra_big(ro_stft *h, const void *d_iq, int format, int64_t first_row, int64_t rows, float2 *d_out,
                        int64_t out_stride, hipStream_t s);
+
+// ---- ro_snapshots.cpp
+// what every call that takes a row ring asks of it (null: refused too), as a refusal in the name of `who`
+int ring_check(const char *who, const ro_row_ring_t *ring);
 
 // ---- ro_czt.cpp
 int czt_length(int bins);                       // the inner power-of-two length of an even bins that is not one, else 0

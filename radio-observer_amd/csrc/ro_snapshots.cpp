@@ -9,10 +9,8 @@ using namespace ro::host;
 static_assert(sizeof(ro_row_ring_t) == 32 && sizeof(ro_snapshot_t) == 72 && sizeof(ro_snap_summary_t) == 64,
               "the snapshots' structs are ABI");
 
-namespace {
-
-// what the calls ask of a ring (null: refused too), as a refusal in the name of `who`
-int ring_check(const char *who, const ro_row_ring_t *ring)
+// what the calls ask of a ring (null: refused too), as a refusal in the name of `who` (ro_periodic.cpp asks the same)
+int ro::host::ring_check(const char *who, const ro_row_ring_t *ring)
 {
     if (!ring) return fail(RO_ERR_INVALID, "%s: null ring", who);
     if (!ring->d_rows) return fail(RO_ERR_INVALID, "%s: ring: null d_rows", who);
@@ -22,6 +20,8 @@ int ring_check(const char *who, const ro_row_ring_t *ring)
                     ring->reserved);
     return RO_OK;
 }
+
+namespace {
 
 // what ro_snapshots_host and ro_stft_snapshots_resident ask of their common arguments, as a refusal in the name of `who`;
 // d: "d_" where the arrays are the device's (the argument names of the resident call), "" on the host.  *slots: the mask's
