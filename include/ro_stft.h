@@ -911,6 +911,77 @@ int ro_stft_periodic_units_resident(ro_stft_t *h, const ro_row_ring_t *ring, con
 int ro_periodic_units_host(const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count,
                            const ro_periodic_entry_t *dir, int64_t entries, void *units, int64_t units_bytes);
 
+/* ---- grey-level previews: each snapshot's ln image as uint8 -------------------------
+ * What the stations make of every one of those files next: fits2png's natural log of the non-zero pixels, the image's own
+ * min / max of it and (ln - min) / (max - min) * 255 as one byte per pixel (fits2png:46, :444-445, :476-502).  The two
+ * calls here make that preview for every image of a snapshot directory and of a periodic plan, a quarter of the units'
+ * bytes to download.
+ * Geometry: a level image of naxis1 x naxis2 pixels occupies naxis1 naxis2 bytes, row-major with stride naxis1, the first
+ * FFT row first, and is zero-padded to a multiple of RO_LEVEL_BLOCK bytes.  ceil(p / 720) = ceil(4 p / 2880): an image has
+ * exactly as many 720-byte blocks as its FITS unit has 2880-byte ones, and packed the same way it sits at a quarter of its
+ * unit's offset.  d_levels is aligned to 16 bytes, and so is every image (720 = 16 x 45).
+ * Pixel rule, that of ro_stft_ln_tile_resident, bit for bit: l = logf(v) in float32; the range is the min / max of l over
+ * the image's pixels with v != 0; level = (v != 0 && max > min) ? (uint8)(int)((l - min) / (max - min) * 255.f) : 0, all in
+ * float32.  An image without a non-zero pixel has the range {+inf, -inf} and all levels 0.  Pixels that are NaN, +-inf or
+ * negative are not pinned. */
+#define RO_LEVEL_BLOCK 720                     /* bytes = pixels; RO_FITS_BLOCK / 4 */
+
+typedef struct ro_level_range {    /* 8 bytes: the colour range of one image */
+    float ln_min, ln_max;          /* min / max of logf over its non-zero pixels; +inf, -inf without one */
+} ro_level_range_t;
+
+/* The level images of one snapshot arena.  The arguments of ro_stft_snapshot_units_resident, with
+ *   d_level_dir      room for dir_capacity entries, in LEVEL terms: offset is bytes into d_levels, a multiple of 720; bytes =
+ *                    naxis1 naxis2.  With levels_bytes = units_bytes / 4 it is the unit directory with offset and bytes
+ *                    divided by four.  Entries at or behind n are not touched
+ *   d_ranges         room for dir_capacity entries (NULL with dir_capacity = 0): d_ranges[d] is entry d's range if it is
+ *                    WRITTEN and {0, 0} otherwise, for d < n; entries at or behind n are not touched
+ *   d_levels, levels_bytes   the images, aligned to 16 bytes; NULL with levels_bytes = 0
+ *   d_level_summary  one entry; units_bytes and needed_bytes count level bytes (needed_bytes sizes a second call)
+ * Entry rules 1 - 4 of ro_stft_snapshot_units_resident apply unchanged, in order; the entry count is read on the device; the
+ * prefix rule is the same over 720-byte blocks with the room levels_bytes; the statuses are RO_UNIT_*; NO_ROOM entries carry
+ * their shape with offset 0.  Bytes of d_levels past the summary's units_bytes are not touched; the sources are only read;
+ * equal inputs give equal bytes.
+ * Plain launches (csrc/ro_levels.hip), no atomics, no workgroup waiting for another: the units' plan; a reduce over the
+ * 720-pixel blocks that leaves each block's min / max in handle scratch; a fold of each entry's blocks into d_ranges; the
+ * store.  Asynchronous on `stream`; the scratch is this call's own (it grows, waiting for the device, with dir_capacity
+ * and with the blocks levels_bytes holds): one call in flight per handle unless they share a stream.
+ * RO_ERR_INVALID, before anything is launched, the text naming the argument: as ro_stft_snapshot_units_resident refuses
+ * (d_level_dir, d_levels, levels_bytes and d_level_summary in the place of the units' arguments); d_ranges == NULL with
+ * dir_capacity > 0; [d_levels, + levels_bytes) overlapping the arena; levels_bytes above 2^61. */
+int ro_stft_snapshot_levels_resident(ro_stft_t *h, const ro_snapshot_t *d_dir, int64_t dir_capacity,
+                                     const ro_snap_summary_t *d_snap_summary, const float *d_arena, int64_t arena_floats,
+                                     int32_t cols, const ro_band_window_t *slot_windows,
+                                     ro_fits_unit_t *d_level_dir, ro_level_range_t *d_ranges, void *d_levels,
+                                     int64_t levels_bytes, ro_unit_summary_t *d_level_summary, void *stream);
+
+/* The level images of one periodic plan.  dir is HOST memory, exactly what ro_periodic_plan left for the units (the plan
+ * cannot be asked twice: next_index advances), so the levels ride on the units' plan: the image of a WRITTEN entry e sits
+ * at e.offset / 4 of d_levels, d_ranges[e] (device, `entries` of them) is written for WRITTEN entries and not touched for
+ * the others, and levels_bytes must hold a quarter of the end of the last WRITTEN unit.  Only scalars reach the kernels:
+ * three launches (reduce, fold, store), no plan kernel, no directory upload; handle scratch for the blocks' min / max (a
+ * block of this call's own).  The ring is only read; bytes of d_levels behind the last written image are not touched; no
+ * atomics: equal inputs give equal bytes.  Asynchronous on `stream`: issue it behind ro_stft_ring_put_resident, next to
+ * ro_stft_periodic_units_resident.  entries == 0, or none WRITTEN, launches nothing.
+ * RO_ERR_INVALID, before anything is launched, the text naming the argument: as ro_stft_periodic_units_resident refuses,
+ * the directory's consistency included (d_levels and levels_bytes in the place of d_units and units_bytes; the WRITTEN
+ * entries' units lie inside 4 x levels_bytes); d_ranges == NULL with a WRITTEN entry; d_levels not aligned to 16 bytes;
+ * [d_levels, + levels_bytes) overlapping the ring. */
+int ro_stft_periodic_levels_resident(ro_stft_t *h, const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count,
+                                     const ro_periodic_entry_t *dir, int64_t entries, ro_level_range_t *d_ranges,
+                                     void *d_levels, int64_t levels_bytes, void *stream);
+
+/* The same rules over host memory (ring->d_rows included): no handle, no device, the C library's logf and ro_ln_levels'
+ * arithmetic.  Directories, summaries, offsets, padding and untouched bytes are those of the device calls; levels and
+ * ranges differ by what the two logf differ.  Refusals as above, without the handle and the alignment. */
+int ro_snapshot_levels_host(const ro_snapshot_t *dir, int64_t dir_capacity, const ro_snap_summary_t *snap_summary,
+                            const float *arena, int64_t arena_floats, int32_t cols, const ro_band_window_t *slot_windows,
+                            ro_fits_unit_t *level_dir, ro_level_range_t *ranges, void *levels, int64_t levels_bytes,
+                            ro_unit_summary_t *level_summary);
+int ro_periodic_levels_host(const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count,
+                            const ro_periodic_entry_t *dir, int64_t entries, ro_level_range_t *ranges, void *levels,
+                            int64_t levels_bytes);
+
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel
  * when records are requested).  kernel_ms_out (optional, 2 floats) receives the

@@ -130,6 +130,10 @@ PERIODIC_SUMMARY_DTYPE = np.dtype([("entries", np.int64), ("written", np.int64),
                                    ("unlisted", np.int64), ("units_bytes", np.int64), ("needed_bytes", np.int64),
                                    ("reserved", np.int64)])
 
+RO_LEVEL_BLOCK = 720
+# ro_level_range_t (8 bytes: the colour range of one level image)
+LEVEL_RANGE_DTYPE = np.dtype([("ln_min", np.float32), ("ln_max", np.float32)])
+
 
 class Config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("bins", C.c_int32), ("overlap", C.c_int32),
@@ -253,6 +257,15 @@ _EXPORTS = {
     "ro_stft_periodic_units_resident": (C.c_int, [C.c_void_p, C.POINTER(RowRing), C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
                                                   C.c_void_p, C.c_int64, C.c_void_p]),
     "ro_periodic_units_host": (C.c_int, [C.POINTER(RowRing), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "ro_stft_snapshot_levels_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                                   C.POINTER(BandWindow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                                   C.c_void_p, C.c_void_p]),
+    "ro_snapshot_levels_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                          C.POINTER(BandWindow), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ro_stft_periodic_levels_resident": (C.c_int, [C.c_void_p, C.POINTER(RowRing), C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                                   C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ro_periodic_levels_host": (C.c_int, [C.POINTER(RowRing), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int64]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -706,6 +719,54 @@ def periodic_units_host(ring, recorders, directory, units_bytes, cols=None):
     return units[:used]
 
 
+def snapshot_levels_host(directory, snap_summary, arena, cols, slot_windows, levels_bytes):
+    """The grey-level previews of one snapshot arena over host memory -- ro_snapshot_levels_host.  The arguments of
+    snapshot_units_host, the room in level bytes.  Returns (level directory, ranges, levels, summary): one FITS_UNIT_DTYPE
+    entry (offsets and bytes in level terms) and one LEVEL_RANGE_DTYPE entry per directory entry, the bytes of the images
+    in use (each naxis1 x naxis2 uint8, zero-padded to 720), a UNIT_SUMMARY_DTYPE scalar."""
+    directory = np.ascontiguousarray(directory)
+    if directory.dtype != SNAPSHOT_DTYPE or directory.ndim != 1 or snap_summary.itemsize != 64 or snap_summary.size < 1:
+        raise ValueError("directory: SNAPSHOT_DTYPE [n] with the summary of the call that wrote them")
+    arena = np.ascontiguousarray(arena)
+    if arena.dtype != np.float32 or arena.ndim != 1:
+        raise ValueError("arena: float32 [arena_floats]")
+    dcap = directory.shape[0]
+    level_dir = np.zeros(max(dcap, 1), FITS_UNIT_DTYPE)
+    ranges = np.zeros(max(dcap, 1), LEVEL_RANGE_DTYPE)
+    levels = np.zeros(max(levels_bytes, 1), np.uint8)
+    out = np.zeros(1, UNIT_SUMMARY_DTYPE)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_snapshot_levels_host(p(directory) if dcap else None, dcap, p(snap_summary), p(arena) if arena.size else None,
+                                             arena.size, cols, _slot_windows(slot_windows), p(level_dir), p(ranges),
+                                             p(levels) if levels_bytes > 0 else None, levels_bytes, p(out)))
+    n = int(out["entries"][0])
+    return level_dir[:n], ranges[:n], levels[:int(out["units_bytes"][0])], out[0]
+
+
+def periodic_levels_host(ring, recorders, directory, levels_bytes, cols=None):
+    """The grey-level previews of one periodic plan over host memory -- ro_periodic_levels_host.  The arguments of
+    periodic_units_host, the room in level bytes (a quarter of the units').  Returns (ranges, levels): one LEVEL_RANGE_DTYPE
+    entry per directory entry (zero where the entry is not WRITTEN) and the bytes of the images in use; the image of a
+    WRITTEN entry e starts at e["offset"] // 4."""
+    ring = np.asarray(ring)
+    if ring.dtype != np.float32 or ring.ndim != 2 or not ring.flags.c_contiguous:
+        raise ValueError("ring: a C-contiguous float32 array [ring_rows, stride]")
+    desc = RowRing(ring.ctypes.data, ring.shape[1], ring.shape[0], ring.shape[1] if cols is None else cols, 0)
+    recs = periodic_recorders(recorders)
+    directory = np.ascontiguousarray(directory)
+    if directory.dtype != PERIODIC_ENTRY_DTYPE or directory.ndim != 1:
+        raise ValueError("directory: PERIODIC_ENTRY_DTYPE [entries]")
+    ranges = np.zeros(max(len(directory), 1), LEVEL_RANGE_DTYPE)
+    levels = np.zeros(max(levels_bytes, 1), np.uint8)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_periodic_levels_host(C.byref(desc), p(recs) if len(recs) else None, len(recs),
+                                             p(directory) if len(directory) else None, len(directory), p(ranges),
+                                             p(levels) if levels_bytes > 0 else None, levels_bytes))
+    written = directory[directory["status"] == RO_PERIODIC_WRITTEN]
+    used = 0 if not len(written) else (int(written[-1]["offset"]) + -(-int(written[-1]["bytes"]) // RO_FITS_BLOCK) * RO_FITS_BLOCK) // 4
+    return ranges[:len(directory)], levels[:used]
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -918,6 +979,32 @@ class Stft:
         _check(library().ro_stft_periodic_units_resident(self._h, C.byref(ring), p(recs) if len(recs) else None, len(recs),
                                                          p(directory) if len(directory) else None, len(directory),
                                                          _ptr(d_units), units_bytes, _ptr(stream)))
+
+    def snapshot_levels_resident(self, d_dir, dir_capacity, d_snap_summary, d_arena, arena_floats, cols, slot_windows,
+                                 d_level_dir, d_ranges, d_levels, levels_bytes, d_level_summary, stream=None):
+        """the grey-level preview of every captured image of d_dir: the viewer's ln image of its slot's columns as one byte
+        per pixel, zero-padded to 720 bytes, packed into d_levels with a directory and each image's range --
+        ro_stft_snapshot_levels_resident.  The sources as snapshot_units_resident takes them; d_level_dir: dir_capacity
+        FITS_UNIT_DTYPE entries (level terms); d_ranges: dir_capacity LEVEL_RANGE_DTYPE entries; d_levels: levels_bytes
+        bytes, aligned to 16; d_level_summary: one UNIT_SUMMARY_DTYPE"""
+        _check(library().ro_stft_snapshot_levels_resident(self._h, _ptr(d_dir), dir_capacity, _ptr(d_snap_summary), _ptr(d_arena),
+                                                          arena_floats, cols, _slot_windows(slot_windows), _ptr(d_level_dir),
+                                                          _ptr(d_ranges), _ptr(d_levels), levels_bytes, _ptr(d_level_summary),
+                                                          _ptr(stream)))
+
+    def periodic_levels_resident(self, ring, recorders, directory, d_ranges, d_levels, levels_bytes, stream=None):
+        """the grey-level preview of every WRITTEN entry of `directory`, cut from the ring's slots to its recorder's
+        columns, at a quarter of the entry's offset of d_levels, its range at d_ranges[entry]: three launches --
+        ro_stft_periodic_levels_resident.  ring, recorders and directory (HOST) as periodic_units_resident takes them;
+        d_ranges: len(directory) LEVEL_RANGE_DTYPE entries; d_levels: levels_bytes bytes, aligned to 16"""
+        recs = periodic_recorders(recorders)
+        directory = np.ascontiguousarray(directory)
+        if directory.dtype != PERIODIC_ENTRY_DTYPE or directory.ndim != 1:
+            raise ValueError("directory: PERIODIC_ENTRY_DTYPE [entries]")
+        p = lambda a: C.c_void_p(a.ctypes.data)
+        _check(library().ro_stft_periodic_levels_resident(self._h, C.byref(ring), p(recs) if len(recs) else None, len(recs),
+                                                          p(directory) if len(directory) else None, len(directory),
+                                                          _ptr(d_ranges), _ptr(d_levels), levels_bytes, _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

@@ -10,6 +10,8 @@
 //   ro_units.cpp         the events' files as FITS data units (ro_units.hip), and their host twins
 //   ro_periodic.cpp      the periodic snapshots' plan (host arithmetic), their data units cut from the ring (ro_periodic.hip)
 //                        and the host twin
+//   ro_levels.cpp        the grey-level previews of the event snapshots and of the periodic snapshots (ro_levels.hip), and
+//                        their host twins
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
@@ -41,6 +43,7 @@
 #include "ro_raw.h"
 #include "ro_units.h"
 #include "ro_periodic.h"
+#include "ro_levels.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -273,6 +276,10 @@ struct ro_stft {
     // grows with dir_capacity; one block for each of the two calls (ro::UNITS_OF_IMAGES, ro::UNITS_OF_RAW), so that they do
     // not share a plan
     DeviceBlock<char> d_units_scratch[2];
+    // grey-level previews: the plan and the blocks' keys of ro_stft_snapshot_levels_resident (ro_levels.h; grows with
+    // dir_capacity and with the blocks levels_bytes holds), and the blocks' keys of ro_stft_periodic_levels_resident (grows
+    // with the blocks of a plan); a block for each call, so that the two of a chunk do not share one
+    DeviceBlock<char> d_levels_scratch[2];
     int cus = 0;                               // the device's compute units (device_cus; 0: not asked for yet)
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
@@ -343,6 +350,85 @@ int launch_spectra_big(ro_stft *h, const void *d_iq, int format, int64_t first_r
 // ---- ro_snapshots.cpp
 // what every call that takes a row ring asks of it (null: refused too), as a refusal in the name of `who`
 int ring_check(const char *who, const ro_row_ring_t *ring);
+
+// ---- ro_units.cpp
+// the argument names a refusal speaks of: the units' calls and the levels' calls (ro_levels.cpp) ask the same of them
+struct UnitNames {
+    const char *dir, *buf, *bytes, *summary;       // "unit_dir", "units", "units_bytes", "unit_summary"
+};
+// what the calls over an arena ask of their common arguments, as a refusal in the name of `who`; d: "d_" where the arrays
+// are the device's (the argument names of the resident calls), "" on the host; raw: the directory is ro_raw_capture_t (no
+// cols, no slot windows); aligned: the device's stores are 16 bytes wide
+int units_check(const char *who, const char *d, const UnitNames &names, bool raw, bool aligned, const void *dir,
+                int64_t dir_capacity, const void *summary, const float *arena, int64_t arena_floats, int32_t cols,
+                const ro_band_window_t *slot_windows, const ro_fits_unit_t *unit_dir, const void *units, int64_t units_bytes,
+                const ro_unit_summary_t *unit_summary);
+// The twins' walk over n entries.  want(d): what source entry d asks for (ro_units.h).  A written entry takes `elem` bytes
+// per pixel in blocks of `block` bytes -- 4 and 2880 for a unit, 1 and 720 for a level image: the same number of blocks --
+// and emit(d, w, dst) writes its elem x naxis1 x naxis2 data bytes; the padding is zeroed here
+template <class Want, class Emit>
+void units_walk(int64_t n, Want want, int64_t elem, int64_t block, Emit emit, ro_fits_unit_t *unit_dir, void *units,
+                int64_t units_bytes, ro_unit_summary_t *unit_summary)
+{
+    ro_unit_summary_t sum{};
+    sum.entries = n;
+    const int64_t room = units_bytes / block;
+    int64_t first_b = 0;                         // blocks of every writable entry so far, fitting or not
+    for (int64_t d = 0; d < n; ++d) {
+        const ro::UnitWant w = want(d);
+        ro_fits_unit_t out{};
+        out.status = w.status;
+        if (w.status == RO_UNIT_SKIPPED) sum.skipped += 1;
+        else if (w.status == RO_UNIT_INVALID) sum.invalid += 1;
+        else {
+            const int64_t blocks = ro::unit_blocks(w.naxis1, w.naxis2);
+            out.bytes = elem * (int64_t)w.naxis1 * w.naxis2;
+            out.naxis2 = w.naxis2;
+            out.naxis1 = w.naxis1;
+            if (first_b + blocks <= room) {
+                out.offset = first_b * block;
+                unsigned char *dst = static_cast<unsigned char *>(units) + out.offset;
+                emit(d, w, dst);
+                std::memset(dst + out.bytes, 0, (size_t)(blocks * block - out.bytes));
+                sum.written += 1;
+                sum.units_bytes = (first_b + blocks) * block;
+            } else {
+                out.status = RO_UNIT_NO_ROOM;
+                sum.no_room += 1;
+            }
+            first_b += blocks;
+        }
+        unit_dir[d] = out;
+    }
+    sum.needed_bytes = first_b * block;
+    *unit_summary = sum;
+}
+// the entries of a source directory: n = min(max(resolved, 0), dir_capacity)
+inline int64_t entries_of(int64_t resolved, int64_t dir_capacity) { return std::min(std::max<int64_t>(resolved, 0), dir_capacity); }
+// what source entry d of an image directory asks for
+inline ro::UnitWant unit_want_snapshot(const ro_snapshot_t &e, int32_t cols, int64_t arena_floats, const ro_band_window_t *slot_windows)
+{
+    const bool slot_ok = e.slot >= 0 && e.slot < ro::UNIT_SLOTS;
+    return ro::unit_want_image(e.status, e.slot, e.rows, e.offset, cols, arena_floats, slot_ok ? slot_windows[e.slot].first_col : 0,
+                               slot_ok ? slot_windows[e.slot].cols : 0);
+}
+// the resident calls' arguments as the plan takes them (ro::UnitsArgs but the scratch)
+void units_fill_args(ro::UnitsArgs &a, const void *dir, int64_t dir_capacity, const void *summary, const float *arena,
+                     int64_t arena_floats, int32_t cols, const ro_band_window_t *slot_windows, ro_fits_unit_t *unit_dir,
+                     void *units, int64_t units_bytes, ro_unit_summary_t *unit_summary);
+
+// ---- ro_periodic.cpp
+// the argument names a refusal speaks of: "units", "units_bytes"; and what the room is to the directory's unit offsets:
+// "" for the units themselves, for the levels that it holds a quarter of them
+struct PeriodicNames {
+    const char *buf, *bytes, *room;
+};
+// what the calls over a plan's directory ask of their common arguments, as a refusal in the name of `who`; d: "d_" for the
+// resident calls' argument names.  The buffer holds `block`-byte blocks, one for each 2880-byte block of the plan's units
+// (2880 for the units, 720 for the levels).  Fills a: the ring and the WRITTEN entries of each recorder as one run
+int periodic_check(const char *who, const char *d, const PeriodicNames &names, int64_t block, bool aligned,
+                   const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count, const ro_periodic_entry_t *dir,
+                   int64_t entries, void *buf, int64_t buf_bytes, ro::PeriodicArgs *a);
 
 // ---- ro_czt.cpp
 int czt_length(int bins);                       // the inner power-of-two length of an even bins that is not one, else 0

@@ -145,6 +145,16 @@ __device__ __forceinline__ int64_t plan_entry(const int64_t *first, int64_t n, i
     return lo - 1;
 }
 
+// The copy's gather out of an arena of rows: float x of a cut that starts in a row at arena float `base` -- x counts from
+// the row's first cut column on, a row of the cut is naxis1 floats and a row of the arena `stride` (x < 2^32, naxis1 >= 1) --
+// clamped into [0, last], so that no load is guarded and none leaves the buffer
+__device__ __forceinline__ int64_t cut_at(int64_t base, unsigned x, unsigned naxis1, int64_t stride, int64_t last)
+{
+    const unsigned dr = x / naxis1;
+    const int64_t at = base + (int64_t)dr * stride + (x - dr * naxis1);
+    return at < 0 ? 0 : (at > last ? last : at);
+}
+
 // this wave among the waves of the copy's grid: it takes items me, me + waves, ...
 struct CopyWave {
     unsigned me, waves;

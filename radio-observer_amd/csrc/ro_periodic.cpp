@@ -31,9 +31,11 @@ int recorders_check(const char *who, const ro_periodic_t *recorders, int count, 
 }
 
 // The directory as the kernel takes it: the WRITTEN entries of each recorder as one run.  Refuses, in the name of `who`,
-// a directory that is not what ro_periodic_plan writes for these recorders
+// a directory that is not what ro_periodic_plan writes for these recorders; room: the blocks the buffer holds, names and
+// buf_bytes: how the refusal speaks of it
 int runs_of(const char *who, const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count,
-            const ro_periodic_entry_t *dir, int64_t entries, int64_t units_bytes, ro::PeriodicArgs *a)
+            const ro_periodic_entry_t *dir, int64_t entries, int64_t room, const PeriodicNames &names, int64_t buf_bytes,
+            ro::PeriodicArgs *a)
 {
     int64_t end = 0;                             // blocks of the WRITTEN entries so far
     bool full = false;                           // a NO_ROOM entry has been seen: nothing behind it is WRITTEN
@@ -64,10 +66,10 @@ int runs_of(const char *who, const ro_row_ring_t *ring, const ro_periodic_t *rec
             continue;
         }
         const int64_t blocks = ro::periodic_blocks(e.naxis1, e.rows);
-        if (full || e.offset != end * RO_FITS_BLOCK || blocks > units_bytes / RO_FITS_BLOCK - end)
+        if (full || e.offset != end * RO_FITS_BLOCK || blocks > room - end)
             return fail(RO_ERR_INVALID, "%s: dir[%lld]: offset %lld: the WRITTEN entries are packed from 0 on in multiples of %d, "
-                        "inside units_bytes %lld, in front of every NO_ROOM one", who, (long long)d, (long long)e.offset,
-                        RO_FITS_BLOCK, (long long)units_bytes);
+                        "inside %s %lld%s, in front of every NO_ROOM one", who, (long long)d, (long long)e.offset,
+                        RO_FITS_BLOCK, names.bytes, (long long)buf_bytes, names.room);
         ro::PeriodicRun &r = a->run[e.recorder];
         if (r.units == 0) {
             r.row0 = e.first_row;
@@ -86,35 +88,43 @@ int runs_of(const char *who, const ro_row_ring_t *ring, const ro_periodic_t *rec
     return RO_OK;
 }
 
-// what the two unit calls ask of their common arguments; d: "d_" for the resident call's argument names
-int units_check(const char *who, const char *d, bool aligned, const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count,
-                const ro_periodic_entry_t *dir, int64_t entries, void *units, int64_t units_bytes, ro::PeriodicArgs *a)
+const PeriodicNames UNITS = {"units", "units_bytes", ""};
+
+}  // namespace
+
+namespace ro {
+namespace host {
+
+int periodic_check(const char *who, const char *d, const PeriodicNames &names, int64_t block, bool aligned,
+                   const ro_row_ring_t *ring, const ro_periodic_t *recorders, int count, const ro_periodic_entry_t *dir,
+                   int64_t entries, void *buf, int64_t buf_bytes, ro::PeriodicArgs *a)
 {
     int rc = ring_check(who, ring);
     if (rc != RO_OK) return rc;
     if ((rc = recorders_check(who, recorders, count, ring->cols)) != RO_OK) return rc;
-    if (entries < 0 || units_bytes < 0)
-        return fail(RO_ERR_INVALID, "%s: entries %lld, units_bytes %lld: neither may be negative", who, (long long)entries,
-                    (long long)units_bytes);
+    if (entries < 0 || buf_bytes < 0)
+        return fail(RO_ERR_INVALID, "%s: entries %lld, %s %lld: neither may be negative", who, (long long)entries, names.bytes,
+                    (long long)buf_bytes);
     if (entries > 0 && !dir) return fail(RO_ERR_INVALID, "%s: null dir with entries %lld", who, (long long)entries);
-    if (units_bytes > 0 && !units)
-        return fail(RO_ERR_INVALID, "%s: null %sunits with units_bytes %lld", who, d, (long long)units_bytes);
-    if (aligned && ((uintptr_t)units & 15u) != 0) return fail(RO_ERR_INVALID, "%s: %sunits is not aligned to 16 bytes", who, d);
-    if (units_bytes > 0) {
-        const uintptr_t u = (uintptr_t)units, r = (uintptr_t)ring->d_rows;
+    if (buf_bytes > 0 && !buf)
+        return fail(RO_ERR_INVALID, "%s: null %s%s with %s %lld", who, d, names.buf, names.bytes, (long long)buf_bytes);
+    if (aligned && ((uintptr_t)buf & 15u) != 0) return fail(RO_ERR_INVALID, "%s: %s%s is not aligned to 16 bytes", who, d, names.buf);
+    if (buf_bytes > 0) {
+        const uintptr_t u = (uintptr_t)buf, r = (uintptr_t)ring->d_rows;
         const uintptr_t ring_bytes = 4 * (uintptr_t)((ring->ring_rows - 1) * ring->stride + ring->cols);
-        if (u < r + ring_bytes && r < u + (uintptr_t)units_bytes)
-            return fail(RO_ERR_INVALID, "%s: %sunits overlaps the ring: the units are written while the ring is read", who, d);
+        if (u < r + ring_bytes && r < u + (uintptr_t)buf_bytes)
+            return fail(RO_ERR_INVALID, "%s: %s%s overlaps the ring: the %s are written while the ring is read", who, d, names.buf,
+                        names.buf);
     }
     a->ring = ring->d_rows;
     a->ring_stride = ring->stride;
     a->ring_rows = ring->ring_rows;
     a->cols = ring->cols;
-    a->units = static_cast<char *>(units);
-    return runs_of(who, ring, recorders, count, dir, entries, units_bytes, a);
+    return runs_of(who, ring, recorders, count, dir, entries, buf_bytes / block, names, buf_bytes, a);
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace ro
 
 extern "C" int ro_snapshot_rows(int sample_rate, int bins, int overlap, int snapshot_length)
 {
@@ -200,8 +210,9 @@ extern "C" int ro_stft_periodic_units_resident(ro_stft_t *h, const ro_row_ring_t
     const char *who = "ro_stft_periodic_units_resident";
     if (!h) return fail(RO_ERR_INVALID, "%s: null handle", who);
     ro::PeriodicArgs a{};
-    int rc = units_check(who, "d_", true, ring, recorders, count, dir, entries, d_units, units_bytes, &a);
+    int rc = periodic_check(who, "d_", UNITS, RO_FITS_BLOCK, true, ring, recorders, count, dir, entries, d_units, units_bytes, &a);
     if (rc != RO_OK) return rc;
+    a.units = static_cast<char *>(d_units);
     if (a.blocks == 0) return RO_OK;
     HIP_TRY(hipSetDevice(h->device));
     int cus = 0;
@@ -216,7 +227,8 @@ extern "C" int ro_periodic_units_host(const ro_row_ring_t *ring, const ro_period
                                       const ro_periodic_entry_t *dir, int64_t entries, void *units, int64_t units_bytes)
 {
     ro::PeriodicArgs a{};
-    const int rc = units_check("ro_periodic_units_host", "", false, ring, recorders, count, dir, entries, units, units_bytes, &a);
+    const int rc = periodic_check("ro_periodic_units_host", "", UNITS, RO_FITS_BLOCK, false, ring, recorders, count, dir, entries, units,
+                                  units_bytes, &a);
     if (rc != RO_OK) return rc;
     const unsigned char *src = reinterpret_cast<const unsigned char *>(ring->d_rows);
     for (int64_t d = 0; d < entries; ++d) {

@@ -85,20 +85,7 @@ __global__ __launch_bounds__(64 * COPY_WAVES) void periodic_copy_kernel(Periodic
 
 hipError_t launch_periodic(const PeriodicArgs &a, int cus, hipStream_t s)
 {
-    if (a.blocks < 0 || !a.ring || a.ring_rows < 1 || a.cols < 1 || a.ring_stride < a.cols || (a.blocks > 0 && !a.units))
-        return hipErrorInvalidValue;
-    int64_t end = 0;                             // the runs pack the blocks from 0 on
-    for (int i = 0; i < RO_MAX_PERIODIC; ++i) {
-        const PeriodicRun &r = a.run[i];
-        if (r.units == 0) continue;
-        if (r.units < 0 || r.block0 != end || r.row0 < 0 || r.snapshot_rows < 1 ||
-            (r.units > 1 ? r.snapshot_rows : r.last_rows) > a.ring_rows ||          // a unit's rows are in the ring at once
-            r.last_rows < 1 || r.last_rows > r.snapshot_rows || r.first_col < 0 || r.naxis1 < 1 ||
-            (int64_t)r.first_col + r.naxis1 > a.cols || r.unit_blocks != periodic_blocks(r.naxis1, r.snapshot_rows))
-            return hipErrorInvalidValue;
-        end += (r.units - 1) * r.unit_blocks + periodic_blocks(r.naxis1, r.last_rows);
-    }
-    if (end != a.blocks) return hipErrorInvalidValue;
+    if (!periodic_runs_ok(a) || (a.blocks > 0 && !a.units)) return hipErrorInvalidValue;
     if (a.blocks == 0) return hipSuccess;
     // the work is known here: no more workgroups than there are blocks for their waves
     const int64_t need = (a.blocks + COPY_WAVES - 1) / COPY_WAVES;

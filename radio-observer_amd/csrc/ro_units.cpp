@@ -9,19 +9,18 @@ using namespace ro::host;
 static_assert(sizeof(ro_fits_unit_t) == 32 && sizeof(ro_unit_summary_t) == 64 && RO_FITS_BLOCK == 2880,
               "the units' structs are ABI");
 
-namespace {
+namespace ro {
+namespace host {
 
-// what the four calls ask of their common arguments, as a refusal in the name of `who`; d: "d_" where the arrays are the
-// device's (the argument names of the resident calls), "" on the host; raw: the directory is ro_raw_capture_t (no cols, no
-// slot windows); aligned: the device's stores are 16 bytes wide
-int units_check(const char *who, const char *d, bool raw, bool aligned, const void *dir, int64_t dir_capacity,
-                const void *summary, const float *arena, int64_t arena_floats, int32_t cols, const ro_band_window_t *slot_windows,
-                const ro_fits_unit_t *unit_dir, const void *units, int64_t units_bytes, const ro_unit_summary_t *unit_summary)
+int units_check(const char *who, const char *d, const UnitNames &names, bool raw, bool aligned, const void *dir,
+                int64_t dir_capacity, const void *summary, const float *arena, int64_t arena_floats, int32_t cols,
+                const ro_band_window_t *slot_windows, const ro_fits_unit_t *unit_dir, const void *units, int64_t units_bytes,
+                const ro_unit_summary_t *unit_summary)
 {
     const char *dir_name = raw ? "raw_dir" : "dir", *sum_name = raw ? "raw_summary" : "snap_summary";
     if (dir_capacity < 0 || arena_floats < 0 || units_bytes < 0)
-        return fail(RO_ERR_INVALID, "%s: dir_capacity %lld, arena_floats %lld, units_bytes %lld: none may be negative", who,
-                    (long long)dir_capacity, (long long)arena_floats, (long long)units_bytes);
+        return fail(RO_ERR_INVALID, "%s: dir_capacity %lld, arena_floats %lld, %s %lld: none may be negative", who,
+                    (long long)dir_capacity, (long long)arena_floats, names.bytes, (long long)units_bytes);
     if (!summary) return fail(RO_ERR_INVALID, "%s: null %s%s", who, d, sum_name);
     if (dir_capacity > 0 && !dir)
         return fail(RO_ERR_INVALID, "%s: null %s%s with dir_capacity %lld", who, d, dir_name, (long long)dir_capacity);
@@ -40,17 +39,46 @@ int units_check(const char *who, const char *d, bool raw, bool aligned, const vo
         }
     }
     if (!unit_dir || !unit_summary)
-        return fail(RO_ERR_INVALID, "%s: null %s%s", who, d, !unit_dir ? "unit_dir" : "unit_summary");
+        return fail(RO_ERR_INVALID, "%s: null %s%s", who, d, !unit_dir ? names.dir : names.summary);
     if (units_bytes > 0 && !units)
-        return fail(RO_ERR_INVALID, "%s: null %sunits with units_bytes %lld", who, d, (long long)units_bytes);
-    if (aligned && ((uintptr_t)units & 15u) != 0) return fail(RO_ERR_INVALID, "%s: %sunits is not aligned to 16 bytes", who, d);
+        return fail(RO_ERR_INVALID, "%s: null %s%s with %s %lld", who, d, names.buf, names.bytes, (long long)units_bytes);
+    if (aligned && ((uintptr_t)units & 15u) != 0)
+        return fail(RO_ERR_INVALID, "%s: %s%s is not aligned to 16 bytes", who, d, names.buf);
     if (units_bytes > 0 && arena_floats > 0) {
         const uintptr_t u = (uintptr_t)units, a = (uintptr_t)arena;
         if (u < a + 4 * (uintptr_t)arena_floats && a < u + (uintptr_t)units_bytes)
-            return fail(RO_ERR_INVALID, "%s: %sunits overlaps %sarena: the units are written while the arena is read", who, d, d);
+            return fail(RO_ERR_INVALID, "%s: %s%s overlaps %sarena: the %s are written while the arena is read", who, d, names.buf,
+                        d, names.buf);
     }
     return RO_OK;
 }
+
+void units_fill_args(ro::UnitsArgs &a, const void *dir, int64_t dir_capacity, const void *summary, const float *arena,
+                     int64_t arena_floats, int32_t cols, const ro_band_window_t *slot_windows, ro_fits_unit_t *unit_dir,
+                     void *units, int64_t units_bytes, ro_unit_summary_t *unit_summary)
+{
+    a.dir = dir;
+    a.resolved = static_cast<const int64_t *>(summary);           // `resolved` is the first word of both summaries
+    a.dir_capacity = dir_capacity;
+    a.arena = arena;
+    a.arena_floats = arena_floats;
+    a.cols = cols;
+    for (int i = 0; i < ro::UNIT_SLOTS && slot_windows; ++i) {
+        a.win_first[i] = slot_windows[i].first_col;
+        a.win_cols[i] = slot_windows[i].cols;
+    }
+    a.unit_dir = unit_dir;
+    a.units = static_cast<char *>(units);
+    a.units_bytes = units_bytes;
+    a.summary = unit_summary;
+}
+
+}  // namespace host
+}  // namespace ro
+
+namespace {
+
+const UnitNames UNITS = {"unit_dir", "units", "units_bytes", "unit_summary"};
 
 int units_launch(ro_stft_t *h, ro::UnitsArgs &a, int kind, void *stream)
 {
@@ -64,75 +92,25 @@ int units_launch(ro_stft_t *h, ro::UnitsArgs &a, int kind, void *stream)
     return RO_OK;
 }
 
-// The twins' walk.  want(d): what source entry d asks for (ro_units.h); the unit of a written one is made here, float by
-// float: the four bytes of arena float first + r stride + c, reversed
-template <class Want>
-void units_walk(int64_t n, Want want, const float *arena, int64_t stride, ro_fits_unit_t *unit_dir, void *units,
-                int64_t units_bytes, ro_unit_summary_t *unit_summary)
+// the unit of a written entry, float by float: the four bytes of arena float first + r stride + c, reversed
+auto swapped_floats(const float *arena, int64_t stride)
 {
-    ro_unit_summary_t sum{};
-    sum.entries = n;
-    const int64_t room = units_bytes / RO_FITS_BLOCK;
-    int64_t first_b = 0;                         // blocks of every writable entry so far, fitting or not
-    for (int64_t d = 0; d < n; ++d) {
-        const ro::UnitWant w = want(d);
-        ro_fits_unit_t out{};
-        out.status = w.status;
-        if (w.status == RO_UNIT_SKIPPED) sum.skipped += 1;
-        else if (w.status == RO_UNIT_INVALID) sum.invalid += 1;
-        else {
-            const int64_t blocks = ro::unit_blocks(w.naxis1, w.naxis2);
-            out.bytes = 4 * (int64_t)w.naxis1 * w.naxis2;
-            out.naxis2 = w.naxis2;
-            out.naxis1 = w.naxis1;
-            if (first_b + blocks <= room) {
-                out.offset = first_b * RO_FITS_BLOCK;
-                unsigned char *dst = static_cast<unsigned char *>(units) + out.offset;
-                const unsigned char *src = reinterpret_cast<const unsigned char *>(arena);
-                for (int64_t r = 0; r < w.naxis2; ++r)
-                    for (int64_t c = 0; c < w.naxis1; ++c, dst += 4) {
-                        const unsigned char *f = src + 4 * (w.first + r * stride + c);
-                        dst[0] = f[3];
-                        dst[1] = f[2];
-                        dst[2] = f[1];
-                        dst[3] = f[0];
-                    }
-                std::memset(dst, 0, (size_t)(blocks * RO_FITS_BLOCK - out.bytes));
-                sum.written += 1;
-                sum.units_bytes = (first_b + blocks) * RO_FITS_BLOCK;
-            } else {
-                out.status = RO_UNIT_NO_ROOM;
-                sum.no_room += 1;
+    return [=](int64_t, const ro::UnitWant &w, unsigned char *dst) {
+        const unsigned char *src = reinterpret_cast<const unsigned char *>(arena);
+        for (int64_t r = 0; r < w.naxis2; ++r)
+            for (int64_t c = 0; c < w.naxis1; ++c, dst += 4) {
+                const unsigned char *f = src + 4 * (w.first + r * stride + c);
+                dst[0] = f[3];
+                dst[1] = f[2];
+                dst[2] = f[1];
+                dst[3] = f[0];
             }
-            first_b += blocks;
-        }
-        unit_dir[d] = out;
-    }
-    sum.needed_bytes = first_b * RO_FITS_BLOCK;
-    *unit_summary = sum;
-}
-
-int64_t entries_of(int64_t resolved, int64_t dir_capacity) { return std::min(std::max<int64_t>(resolved, 0), dir_capacity); }
-
-void fill_args(ro::UnitsArgs &a, const void *dir, int64_t dir_capacity, const void *summary, const float *arena,
-               int64_t arena_floats, int32_t cols, ro_fits_unit_t *unit_dir, void *units, int64_t units_bytes,
-               ro_unit_summary_t *unit_summary)
-{
-    a.dir = dir;
-    a.resolved = static_cast<const int64_t *>(summary);           // `resolved` is the first word of both summaries
-    a.dir_capacity = dir_capacity;
-    a.arena = arena;
-    a.arena_floats = arena_floats;
-    a.cols = cols;
-    a.unit_dir = unit_dir;
-    a.units = static_cast<char *>(units);
-    a.units_bytes = units_bytes;
-    a.summary = unit_summary;
+    };
 }
 
 }  // namespace
 
-static_assert(offsetof(ro_snap_summary_t, resolved) == 0 && offsetof(ro_raw_summary_t, resolved) == 0, "fill_args reads it there");
+static_assert(offsetof(ro_snap_summary_t, resolved) == 0 && offsetof(ro_raw_summary_t, resolved) == 0, "units_fill_args reads it there");
 
 extern "C" int ro_stft_snapshot_units_resident(ro_stft_t *h, const ro_snapshot_t *d_dir, int64_t dir_capacity,
                                                const ro_snap_summary_t *d_snap_summary, const float *d_arena,
@@ -142,15 +120,12 @@ extern "C" int ro_stft_snapshot_units_resident(ro_stft_t *h, const ro_snapshot_t
 {
     const char *who = "ro_stft_snapshot_units_resident";
     if (!h) return fail(RO_ERR_INVALID, "%s: null handle", who);
-    const int rc = units_check(who, "d_", false, true, d_dir, dir_capacity, d_snap_summary, d_arena, arena_floats, cols, slot_windows,
+    const int rc = units_check(who, "d_", UNITS, false, true, d_dir, dir_capacity, d_snap_summary, d_arena, arena_floats, cols, slot_windows,
                                d_unit_dir, d_units, units_bytes, d_unit_summary);
     if (rc != RO_OK) return rc;
     ro::UnitsArgs a{};
-    fill_args(a, d_dir, dir_capacity, d_snap_summary, d_arena, arena_floats, cols, d_unit_dir, d_units, units_bytes, d_unit_summary);
-    for (int i = 0; i < ro::UNIT_SLOTS; ++i) {
-        a.win_first[i] = slot_windows[i].first_col;
-        a.win_cols[i] = slot_windows[i].cols;
-    }
+    units_fill_args(a, d_dir, dir_capacity, d_snap_summary, d_arena, arena_floats, cols, slot_windows, d_unit_dir, d_units, units_bytes,
+                    d_unit_summary);
     return units_launch(h, a, ro::UNITS_OF_IMAGES, stream);
 }
 
@@ -161,11 +136,12 @@ extern "C" int ro_stft_raw_units_resident(ro_stft_t *h, const ro_raw_capture_t *
 {
     const char *who = "ro_stft_raw_units_resident";
     if (!h) return fail(RO_ERR_INVALID, "%s: null handle", who);
-    const int rc = units_check(who, "d_", true, true, d_raw_dir, dir_capacity, d_raw_summary, d_arena, arena_floats, 2, nullptr,
+    const int rc = units_check(who, "d_", UNITS, true, true, d_raw_dir, dir_capacity, d_raw_summary, d_arena, arena_floats, 2, nullptr,
                                d_unit_dir, d_units, units_bytes, d_unit_summary);
     if (rc != RO_OK) return rc;
     ro::UnitsArgs a{};
-    fill_args(a, d_raw_dir, dir_capacity, d_raw_summary, d_arena, arena_floats, 2, d_unit_dir, d_units, units_bytes, d_unit_summary);
+    units_fill_args(a, d_raw_dir, dir_capacity, d_raw_summary, d_arena, arena_floats, 2, nullptr, d_unit_dir, d_units, units_bytes,
+                    d_unit_summary);
     return units_launch(h, a, ro::UNITS_OF_RAW, stream);
 }
 
@@ -174,15 +150,12 @@ extern "C" int ro_snapshot_units_host(const ro_snapshot_t *dir, int64_t dir_capa
                                       const ro_band_window_t *slot_windows, ro_fits_unit_t *unit_dir, void *units,
                                       int64_t units_bytes, ro_unit_summary_t *unit_summary)
 {
-    const int rc = units_check("ro_snapshot_units_host", "", false, false, dir, dir_capacity, snap_summary, arena, arena_floats, cols,
+    const int rc = units_check("ro_snapshot_units_host", "", UNITS, false, false, dir, dir_capacity, snap_summary, arena, arena_floats, cols,
                                slot_windows, unit_dir, units, units_bytes, unit_summary);
     if (rc != RO_OK) return rc;
-    units_walk(entries_of(snap_summary->resolved, dir_capacity), [&](int64_t d) {
-        const ro_snapshot_t &e = dir[d];
-        const bool slot_ok = e.slot >= 0 && e.slot < ro::UNIT_SLOTS;
-        return ro::unit_want_image(e.status, e.slot, e.rows, e.offset, cols, arena_floats,
-                                   slot_ok ? slot_windows[e.slot].first_col : 0, slot_ok ? slot_windows[e.slot].cols : 0);
-    }, arena, cols, unit_dir, units, units_bytes, unit_summary);
+    units_walk(entries_of(snap_summary->resolved, dir_capacity),
+               [&](int64_t d) { return unit_want_snapshot(dir[d], cols, arena_floats, slot_windows); }, 4, RO_FITS_BLOCK,
+               swapped_floats(arena, cols), unit_dir, units, units_bytes, unit_summary);
     return RO_OK;
 }
 
@@ -190,12 +163,12 @@ extern "C" int ro_raw_units_host(const ro_raw_capture_t *raw_dir, int64_t dir_ca
                                  const float *arena, int64_t arena_floats, ro_fits_unit_t *unit_dir, void *units,
                                  int64_t units_bytes, ro_unit_summary_t *unit_summary)
 {
-    const int rc = units_check("ro_raw_units_host", "", true, false, raw_dir, dir_capacity, raw_summary, arena, arena_floats, 2,
+    const int rc = units_check("ro_raw_units_host", "", UNITS, true, false, raw_dir, dir_capacity, raw_summary, arena, arena_floats, 2,
                                nullptr, unit_dir, units, units_bytes, unit_summary);
     if (rc != RO_OK) return rc;
     units_walk(entries_of(raw_summary->resolved, dir_capacity), [&](int64_t d) {
         const ro_raw_capture_t &e = raw_dir[d];
         return ro::unit_want_raw(e.status, e.samples, e.offset, arena_floats);
-    }, arena, 2, unit_dir, units, units_bytes, unit_summary);
+    }, 4, RO_FITS_BLOCK, swapped_floats(arena, 2), unit_dir, units, units_bytes, unit_summary);
     return RO_OK;
 }

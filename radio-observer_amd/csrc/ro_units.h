@@ -106,5 +106,7 @@ void units_scratch_layout(UnitsArgs &a, void *scratch);
 // the plan and the copy on `s`: two launches; kind: UNITS_OF_IMAGES or UNITS_OF_RAW; cus: the device's compute units (the
 // copy's grid is four workgroups for each)
 hipError_t launch_units(const UnitsArgs &a, int kind, int cus, hipStream_t s);
+// the plan alone, for a caller with a copy of its own (ro_levels.hip): a.units is not looked at, a.units_bytes is the room
+hipError_t launch_units_plan(const UnitsArgs &a, int kind, hipStream_t s);
 
 }  // namespace ro

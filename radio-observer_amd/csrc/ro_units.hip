@@ -130,13 +130,10 @@ __device__ __forceinline__ void block_floats(const unsigned *arena, int64_t last
     for (int s = 0; s < STEPS; ++s) {
         const unsigned t = (unsigned)(lane + 64 * s);
         int64_t at;
-        if (FLAT) at = base + t;
-        else {
-            const unsigned x = c0 + t;           // c0 < naxis1 < 2^31 and t < 768
-            const unsigned dr = x / naxis1;
-            at = base + (int64_t)dr * stride + (x - dr * naxis1);
-        }
-        at = at < 0 ? 0 : (at > last ? last : at);
+        if (FLAT) {
+            at = base + t;
+            at = at < 0 ? 0 : (at > last ? last : at);
+        } else at = cut_at(base, c0 + t, naxis1, stride, last);      // c0 < naxis1 < 2^31 and t < 768
         v[s] = arena[at];
     }
 #pragma unroll
@@ -197,17 +194,39 @@ void units_scratch_layout(UnitsArgs &a, void *scratch)
     a.first_float = a.first_block + a.dir_capacity;
 }
 
-hipError_t launch_units(const UnitsArgs &a, int kind, int cus, hipStream_t s)
+namespace {
+
+// what the plan reads of its arguments
+bool plan_args_ok(const UnitsArgs &a, int kind)
 {
     if ((kind != UNITS_OF_IMAGES && kind != UNITS_OF_RAW) || a.dir_capacity < 0 || a.dir_capacity > UNITS_MAX_ENTRIES ||
         (a.dir_capacity > 0 && !a.dir) || !a.resolved || a.arena_floats < 0 || (a.arena_floats > 0 && !a.arena) || a.cols < 1 ||
-        !a.unit_dir || a.units_bytes < 0 || (a.units_bytes > 0 && !a.units) || ((uintptr_t)a.units & 15u) != 0 || !a.summary ||
-        !a.head || !a.first_block || !a.first_float)
-        return hipErrorInvalidValue;
+        !a.unit_dir || a.units_bytes < 0 || !a.summary || !a.head || !a.first_block || !a.first_float)
+        return false;
     for (int i = 0; i < UNIT_SLOTS && kind == UNITS_OF_IMAGES; ++i)
-        if (a.win_first[i] < 0 || a.win_cols[i] < 0 || (int64_t)a.win_first[i] + a.win_cols[i] > a.cols) return hipErrorInvalidValue;
+        if (a.win_first[i] < 0 || a.win_cols[i] < 0 || (int64_t)a.win_first[i] + a.win_cols[i] > a.cols) return false;
+    return true;
+}
+
+void plan_launch(const UnitsArgs &a, int kind, hipStream_t s)
+{
     if (kind == UNITS_OF_IMAGES) hipLaunchKernelGGL(units_plan_kernel<UNITS_OF_IMAGES>, dim3(1), dim3(T), 0, s, a);
     else hipLaunchKernelGGL(units_plan_kernel<UNITS_OF_RAW>, dim3(1), dim3(T), 0, s, a);
+}
+
+}  // namespace
+
+hipError_t launch_units_plan(const UnitsArgs &a, int kind, hipStream_t s)
+{
+    if (!plan_args_ok(a, kind)) return hipErrorInvalidValue;
+    plan_launch(a, kind, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_units(const UnitsArgs &a, int kind, int cus, hipStream_t s)
+{
+    if (!plan_args_ok(a, kind) || (a.units_bytes > 0 && !a.units) || ((uintptr_t)a.units & 15u) != 0) return hipErrorInvalidValue;
+    plan_launch(a, kind, s);
     hipLaunchKernelGGL(units_copy_kernel, dim3(copy_grid(cus)), dim3(64 * COPY_WAVES), 0, s, a);
     return hipGetLastError();
 }
