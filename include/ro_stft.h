@@ -982,6 +982,82 @@ int ro_periodic_levels_host(const ro_row_ring_t *ring, const ro_periodic_t *reco
                             const ro_periodic_entry_t *dir, int64_t entries, ro_level_range_t *ranges, void *levels,
                             int64_t levels_bytes);
 
+/* ---- preview files: each level image as a complete PNG ------------------------------
+ * What a station publishes of a preview is a .png.  One call turns every level image of a level directory into the bytes
+ * of that file: 8 bit, grey, no interlace; a filter byte 0 in front of every scanline; the zlib stream in STORED deflate
+ * blocks (no compression: LZ77, Huffman and filter choice stay out of scope, and so do fits2png's legend and axes and its
+ * --width); the Adler-32, the IDAT CRC-32, IEND.  A host downloads the files in use and makes one fwrite per file.
+ * For an image of W = naxis1 by H = naxis2 pixels: R = H (W + 1) raw bytes, the first FFT row first, in nblk =
+ * ceil(R / 65535) stored blocks, every one but the last of exactly 65535 bytes:
+ *   89 50 4E 47 0D 0A 1A 0A                                   the signature, 8 bytes
+ *   00 00 00 0D "IHDR" W(be32) H(be32) 08 00 00 00 00 crc     25 bytes
+ *   len(be32) "IDAT"                                          len = 6 + 5 nblk + R
+ *     78 01                                                   the zlib header
+ *     nblk x { BFINAL (01 on the last, else 00), LEN (le16), ~LEN (le16), LEN raw bytes }
+ *     adler32(be32) over the R raw bytes
+ *   crc(be32) over "IDAT" and its data
+ *   00 00 00 00 49 45 4E 44 AE 42 60 82                       IEND
+ * 63 + 5 nblk + R bytes.  Block k's header sits at file byte 43 + 65540 k and its raw bytes at 48 + 65540 k.  An image
+ * whose IDAT length would exceed 2^31 - 1 cannot be a PNG. */
+#define RO_PNG_ALIGN 16                        /* bytes: where a file starts in the buffer */
+
+/* The bytes of that file, or RO_ERR_INVALID for naxis1 < 1, naxis2 < 1 or an IDAT beyond 2^31 - 1.  Pure host. */
+int64_t ro_png_bytes(int32_t naxis1, int64_t naxis2);
+
+/* The files of one level directory.
+ *   d_level_dir, dir_capacity, d_level_summary   the directory and the summary of ro_stft_snapshot_levels_resident, as it
+ *                    leaves them (or the upload of what ro_periodic_level_dir makes of a periodic plan); the number of
+ *                    entries is read ON THE DEVICE: n = min(max(d_level_summary->entries, 0), dir_capacity)
+ *   d_levels, levels_bytes   the level images; NULL with levels_bytes = 0
+ *   d_png_dir        room for dir_capacity entries; entry d describes d_level_dir[d], for d < n: offset is bytes into
+ *                    d_png, a multiple of RO_PNG_ALIGN; bytes is the file's exact size; naxis1 and naxis2 are the image's.
+ *                    Entries at or behind n are not touched
+ *   d_png, png_bytes the files, aligned to 16 bytes; NULL with png_bytes = 0
+ *   d_png_summary    one entry; units_bytes is the end of the last written file rounded up to 16, needed_bytes the room
+ *                    that holds every writable one
+ * For entry d < n, in this order:
+ *   1  status != RO_UNIT_WRITTEN       RO_UNIT_SKIPPED
+ *   2  naxis1 < 1, naxis2 < 1, bytes != naxis1 naxis2, offset < 0, offset not a multiple of RO_LEVEL_BLOCK, offset + bytes >
+ *      levels_bytes, or a shape ro_png_bytes refuses
+ *                                      RO_UNIT_INVALID: nothing of it is read from the levels
+ *   3  otherwise                       WRITABLE: its file occupies ro_png_bytes rounded up to 16
+ * `offset` is the exclusive prefix sum of those rounded sizes over all writable entries in directory order, fitting or not
+ * (the family's prefix rule).  A writable entry with offset + its rounded size <= png_bytes is RO_UNIT_WRITTEN, the others
+ * RO_UNIT_NO_ROOM: they carry naxis1, naxis2 and bytes, with offset 0.  SKIPPED and INVALID entries are zero but for the
+ * status.  The bytes between a file's end and the next multiple of 16 are zero.  Bytes of d_png past the summary's
+ * units_bytes are not touched; the sources are only read; equal inputs give equal bytes.  n == 0 is RO_OK with a zero summary.
+ * Three plain launches (csrc/ro_png.hip), no atomics, no workgroup waiting for another: the plan; a workgroup per stored
+ * block that writes its header and raw bytes and leaves what it adds to the two checksums in handle scratch; a wave per
+ * file that adds those up and writes the Adler-32, the CRC, IEND and the pad.  Asynchronous on `stream`; the scratch is
+ * this call's own (it grows, waiting for the device, with dir_capacity and with png_bytes): one call in flight per handle
+ * unless they share a stream.  A chunk is ... ro_stft_snapshot_levels_resident, then this call, then one download.
+ * RO_ERR_INVALID, before anything is launched, the text naming the argument: a null handle, d_level_summary, d_png_dir or
+ * d_png_summary; d_level_dir == NULL with dir_capacity > 0; d_levels == NULL with levels_bytes > 0; d_png == NULL with
+ * png_bytes > 0; d_png not aligned to 16 bytes; a negative dir_capacity, levels_bytes or png_bytes; dir_capacity > 2^24;
+ * [d_png, + png_bytes) overlapping the levels. */
+int ro_stft_levels_png_resident(ro_stft_t *h, const ro_fits_unit_t *d_level_dir, int64_t dir_capacity,
+                                const ro_unit_summary_t *d_level_summary, const void *d_levels, int64_t levels_bytes,
+                                ro_fits_unit_t *d_png_dir, void *d_png, int64_t png_bytes,
+                                ro_unit_summary_t *d_png_summary, void *stream);
+
+/* The same rules over host memory, entry by entry, with a byte-at-a-time CRC-32 and Adler-32: no handle, no device.  The
+ * yardstick of the device call: equal inputs give equal bytes in every output.  Refusals as above, without the handle and
+ * the alignment. */
+int ro_levels_png_host(const ro_fits_unit_t *level_dir, int64_t dir_capacity, const ro_unit_summary_t *level_summary,
+                       const void *levels, int64_t levels_bytes, ro_fits_unit_t *png_dir, void *png, int64_t png_bytes,
+                       ro_unit_summary_t *png_summary);
+
+/* The directory ro_periodic_plan left, in the level form the call above reads: host arithmetic.  Entry d of level_dir
+ * describes dir[d]: RO_PERIODIC_WRITTEN becomes {offset / 4, bytes = naxis1 rows, naxis2 = rows, naxis1, RO_UNIT_WRITTEN}
+ * -- where ro_stft_periodic_levels_resident puts that entry's image -- RO_PERIODIC_LOST and RO_PERIODIC_NO_ROOM become
+ * RO_UNIT_SKIPPED, zero but for the status.  level_summary counts them (entries, written, skipped) and has a quarter of the
+ * end of the last WRITTEN unit as units_bytes and needed_bytes.  The periodic chain is ... ro_stft_periodic_levels_resident,
+ * the upload of entries x 32 bytes and the summary (the caller's own copy, on the same stream), then
+ * ro_stft_levels_png_resident.  RO_ERR_INVALID: a negative entries; null dir or level_dir with entries > 0; null
+ * level_summary; an entry with an unknown status. */
+int ro_periodic_level_dir(const ro_periodic_entry_t *dir, int64_t entries, ro_fits_unit_t *level_dir,
+                          ro_unit_summary_t *level_summary);
+
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel
  * when records are requested).  kernel_ms_out (optional, 2 floats) receives the

@@ -266,6 +266,12 @@ _EXPORTS = {
                                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ro_periodic_levels_host": (C.c_int, [C.POINTER(RowRing), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_int64]),
+    "ro_png_bytes": (C.c_int64, [C.c_int32, C.c_int64]),
+    "ro_stft_levels_png_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ro_levels_png_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p]),
+    "ro_periodic_level_dir": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -767,6 +773,54 @@ def periodic_levels_host(ring, recorders, directory, levels_bytes, cols=None):
     return ranges[:len(directory)], levels[:used]
 
 
+RO_PNG_ALIGN = 16
+
+
+def png_bytes(naxis1, naxis2):
+    """The bytes of the PNG of a naxis1 x naxis2 level image in stored deflate blocks -- ro_png_bytes: 63 + 5 blocks + raw
+    bytes.  Raises for a shape that cannot be a PNG."""
+    n = int(library().ro_png_bytes(int(naxis1), int(naxis2)))
+    if n < 0:
+        _check(n)
+    return n
+
+
+def levels_png_host(level_dir, level_summary, levels, png_room, dir_capacity=None):
+    """The preview files of one level directory over host memory -- ro_levels_png_host.  level_dir: FITS_UNIT_DTYPE entries in
+    level terms and level_summary: the UNIT_SUMMARY_DTYPE of the call that wrote them (snapshot_levels_host, or
+    periodic_level_dir); levels: uint8; png_room: the room in bytes; dir_capacity: entries of level_dir to look at (None: all).
+    Returns (directory, files, summary): one FITS_UNIT_DTYPE entry per level entry (offset into the files, a multiple of 16;
+    bytes: the file's exact size), the bytes of the files in use, a UNIT_SUMMARY_DTYPE scalar."""
+    level_dir = np.ascontiguousarray(level_dir)
+    level_summary = np.ascontiguousarray(level_summary).reshape(-1)
+    if level_dir.dtype != FITS_UNIT_DTYPE or level_dir.ndim != 1 or level_summary.dtype != UNIT_SUMMARY_DTYPE or level_summary.size < 1:
+        raise ValueError("level_dir: FITS_UNIT_DTYPE [n] with the UNIT_SUMMARY_DTYPE of the call that wrote them")
+    levels = np.ascontiguousarray(levels)
+    if levels.dtype != np.uint8 or levels.ndim != 1:
+        raise ValueError("levels: uint8 [levels_bytes]")
+    dcap = level_dir.shape[0] if dir_capacity is None else dir_capacity
+    png_dir = np.zeros(max(dcap, 1), FITS_UNIT_DTYPE)
+    png = np.zeros(max(png_room, 1), np.uint8)
+    out = np.zeros(1, UNIT_SUMMARY_DTYPE)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_levels_png_host(p(level_dir) if dcap else None, dcap, p(level_summary), p(levels) if levels.size else None,
+                                        levels.size, p(png_dir), p(png) if png_room > 0 else None, png_room, p(out)))
+    return png_dir[:int(out["entries"][0])], png[:int(out["units_bytes"][0])], out[0]
+
+
+def periodic_level_dir(directory):
+    """The directory periodic_plan returned, in the level form levels_png_host and Stft.levels_png_resident read --
+    ro_periodic_level_dir.  Returns (level directory, summary): FITS_UNIT_DTYPE entries, a UNIT_SUMMARY_DTYPE scalar."""
+    directory = np.ascontiguousarray(directory)
+    if directory.dtype != PERIODIC_ENTRY_DTYPE or directory.ndim != 1:
+        raise ValueError("directory: PERIODIC_ENTRY_DTYPE [entries]")
+    level_dir = np.zeros(max(len(directory), 1), FITS_UNIT_DTYPE)
+    out = np.zeros(1, UNIT_SUMMARY_DTYPE)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_periodic_level_dir(p(directory) if len(directory) else None, len(directory), p(level_dir), p(out)))
+    return level_dir[:len(directory)], out[0]
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -1005,6 +1059,16 @@ class Stft:
         _check(library().ro_stft_periodic_levels_resident(self._h, C.byref(ring), p(recs) if len(recs) else None, len(recs),
                                                           p(directory) if len(directory) else None, len(directory),
                                                           _ptr(d_ranges), _ptr(d_levels), levels_bytes, _ptr(stream)))
+
+    def levels_png_resident(self, d_level_dir, dir_capacity, d_level_summary, d_levels, levels_bytes, d_png_dir, d_png,
+                            png_bytes, d_png_summary, stream=None):
+        """Every level image of a level directory as a complete PNG (8 bit grey, stored deflate blocks), each at a multiple
+        of 16 bytes of d_png, with a directory -- ro_stft_levels_png_resident.  d_level_dir / d_level_summary / d_levels as
+        snapshot_levels_resident left them (or the upload of periodic_level_dir); d_png_dir: dir_capacity FITS_UNIT_DTYPE
+        entries; d_png: png_bytes bytes, aligned to 16; d_png_summary: one UNIT_SUMMARY_DTYPE entry"""
+        _check(library().ro_stft_levels_png_resident(self._h, _ptr(d_level_dir), dir_capacity, _ptr(d_level_summary),
+                                                     _ptr(d_levels), levels_bytes, _ptr(d_png_dir), _ptr(d_png), png_bytes,
+                                                     _ptr(d_png_summary), _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

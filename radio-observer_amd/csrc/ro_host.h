@@ -12,6 +12,8 @@
 //                        and the host twin
 //   ro_levels.cpp        the grey-level previews of the event snapshots and of the periodic snapshots (ro_levels.hip), and
 //                        their host twins
+//   ro_png.cpp           the level images as complete PNG files (ro_png.hip), their host twin, and a periodic plan's
+//                        directory in level form
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
@@ -44,6 +46,7 @@
 #include "ro_units.h"
 #include "ro_periodic.h"
 #include "ro_levels.h"
+#include "ro_png.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -280,6 +283,9 @@ struct ro_stft {
     // dir_capacity and with the blocks levels_bytes holds), and the blocks' keys of ro_stft_periodic_levels_resident (grows
     // with the blocks of a plan); a block for each call, so that the two of a chunk do not share one
     DeviceBlock<char> d_levels_scratch[2];
+    // preview files (ro_stft_levels_png_resident): the plan and the stored blocks' checksum parts of one call (ro_png.h);
+    // grows with dir_capacity and with png_bytes
+    DeviceBlock<char> d_png_scratch;
     int cus = 0;                               // the device's compute units (device_cus; 0: not asked for yet)
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
