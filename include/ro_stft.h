@@ -985,8 +985,8 @@ int ro_periodic_levels_host(const ro_row_ring_t *ring, const ro_periodic_t *reco
 /* ---- preview files: each level image as a complete PNG ------------------------------
  * What a station publishes of a preview is a .png.  One call turns every level image of a level directory into the bytes
  * of that file: 8 bit, grey, no interlace; a filter byte 0 in front of every scanline; the zlib stream in STORED deflate
- * blocks (no compression: LZ77, Huffman and filter choice stay out of scope, and so do fits2png's legend and axes and its
- * --width); the Adler-32, the IDAT CRC-32, IEND.  A host downloads the files in use and makes one fwrite per file.
+ * blocks (no compression here: ro_stft_levels_png_deflate_resident below Huffman-codes the blocks; LZ77 and filter choice
+ * stay out of scope, and so do fits2png's legend and axes and its --width); the Adler-32, the IDAT CRC-32, IEND.  A host downloads the files in use and makes one fwrite per file.
  * For an image of W = naxis1 by H = naxis2 pixels: R = H (W + 1) raw bytes, the first FFT row first, in nblk =
  * ceil(R / 65535) stored blocks, every one but the last of exactly 65535 bytes:
  *   89 50 4E 47 0D 0A 1A 0A                                   the signature, 8 bytes
@@ -1046,6 +1046,62 @@ int ro_stft_levels_png_resident(ro_stft_t *h, const ro_fits_unit_t *d_level_dir,
 int ro_levels_png_host(const ro_fits_unit_t *level_dir, int64_t dir_capacity, const ro_unit_summary_t *level_summary,
                        const void *levels, int64_t levels_bytes, ro_fits_unit_t *png_dir, void *png, int64_t png_bytes,
                        ro_unit_summary_t *png_summary);
+
+/* ---- compressed preview files: Huffman-coded deflate blocks ---------------------------
+ * The files above are as large as their pixels.  These two calls write the same files -- same signature, IHDR, one IDAT
+ * with the zlib header 78 01 and the Adler-32 of the raw scanlines, IEND; filter byte 0; the raw bytes cut into blocks of
+ * 65535, the last one shorter -- with every block in the shorter of two forms.  LZ77 matching and filter choice stay out of
+ * scope, and so do fits2png's legend and axes and its --width.  Every block starts on a byte boundary of the stream.
+ *   STORED form    the five-byte header above (BFINAL, LEN, ~LEN) and the raw bytes: 5 + LEN bytes
+ *   HUFFMAN form   BTYPE = 2 with literals only.  The alphabet is the 256 literals and end-of-block (symbol 256); f[0 ... 255]
+ *                  are the frequencies of the block's raw bytes and f[256] = 1, so at least two symbols are used.
+ *     code lengths   The used symbols, sorted by (frequency ascending, symbol ascending), are the leaves of the two-queue
+ *                  Huffman construction: leaves wait in that order, internal nodes in the order they were made, each step
+ *                  joins the two smallest weights, on equal weight a leaf goes before an internal node and an earlier node
+ *                  before a later one.  Of the tree only num[l], the leaves at depth l, is kept.  The limit to 15 bits:
+ *                  every num[l > 15] is added into num[15]; total = sum of num[l] 2^(15 - l); while total != 2^15:
+ *                  decrement num[15], take the largest l < 15 with num[l] > 0, decrement it and add 2 to num[l + 1],
+ *                  decrement total.  Lengths go to the symbols in the order (frequency descending, symbol ascending):
+ *                  first num[1] of them get 1, then num[2] get 2, ...; unused symbols have length 0.  The codes are the
+ *                  canonical ones of RFC 1951 3.2.2.
+ *     header       1106 bits: BFINAL; BTYPE = 2; HLIT = 0 (257 codes); HDIST = 0 (one distance code); HCLEN = 15 (19 entries);
+ *                  the 19 three-bit code-length-code lengths in RFC order (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13,
+ *                  2, 14, 1, 15): 0 for 16, 17 and 18 and 4 for 0 ... 15, so the code of a length v is v in four bits; then
+ *                  258 of those four-bit codes: the 257 lengths, and 0 for the one distance code.  No run-length symbols.
+ *     body         one code per raw byte, then end-of-block's
+ *     ending       a block that is not the file's last: 000 (the header bits of an empty stored block), zero bits up to the
+ *                  byte boundary, 00 00 FF FF.  The last block: zero bits up to the byte boundary.
+ * A block takes the Huffman form exactly when that form, ending included, is shorter in bytes than 5 + LEN.  So a file is
+ * never larger than ro_png_bytes(naxis1, naxis2), which stays the caller's upper bound; IDAT's length is 6 + the blocks'
+ * bytes and the file's 57 more.
+ * The arguments, the entry rules 1 - 3, the prefix rule and the refusals are ro_stft_levels_png_resident's (the text names
+ * this call), with the sizes depending on the data: `bytes` is the file's exact size, files are packed one behind the other
+ * by their ACTUAL rooms (bytes rounded up to RO_PNG_ALIGN), an entry is RO_UNIT_WRITTEN when the rooms up to and including
+ * its own fit in png_bytes and RO_UNIT_NO_ROOM (with its shape and exact bytes, offset 0) otherwise, needed_bytes is the sum
+ * of the actual rooms of all writable entries -- a call with d_png = NULL, png_bytes = 0 is the sizing call -- and
+ * units_bytes the end of the last written file.  One more clause of rule 2: every entry is measured, fitting or not, and
+ * the blocks that can be measured are bounded from the arguments, 2 (levels_bytes / 65535) + 1 + dir_capacity -- what level
+ * images lying side by side in levels_bytes can have.  Counting the blocks of the entries that pass the other clauses in
+ * directory order, the entries from the first one on with which the count passes that bound are RO_UNIT_INVALID (level
+ * images that overlap each other many times over).
+ * Six plain launches (csrc/ro_png_deflate.hip), no global atomics, no floating point, no workgroup waiting for another:
+ * the entry rules and the blocks' prefix; a workgroup per block that counts its bytes, sorts the frequencies, builds the
+ * code and leaves the block's size, form and code table in handle scratch; a wave per file that sums its blocks; the
+ * directory and the summary; a workgroup per block of a written file that assembles the block's bits in LDS, stores them
+ * and leaves what the block adds to the two checksums; a wave per file for the Adler-32, the CRC, IEND and the pad.
+ * Asynchronous on `stream`; the scratch is this call's own (it grows, waiting for the device, with dir_capacity and with
+ * levels_bytes): one call in flight per handle unless they share a stream. */
+int ro_stft_levels_png_deflate_resident(ro_stft_t *h, const ro_fits_unit_t *d_level_dir, int64_t dir_capacity,
+                                        const ro_unit_summary_t *d_level_summary, const void *d_levels, int64_t levels_bytes,
+                                        ro_fits_unit_t *d_png_dir, void *d_png, int64_t png_bytes,
+                                        ro_unit_summary_t *d_png_summary, void *stream);
+
+/* The same rules over host memory, entry by entry and block by block, with a bit writer and a byte-at-a-time CRC-32 and
+ * Adler-32: no handle, no device.  The yardstick of the device call: equal inputs give equal bytes in every output.
+ * Refusals as above, without the handle and the alignment. */
+int ro_levels_png_deflate_host(const ro_fits_unit_t *level_dir, int64_t dir_capacity, const ro_unit_summary_t *level_summary,
+                               const void *levels, int64_t levels_bytes, ro_fits_unit_t *png_dir, void *png, int64_t png_bytes,
+                               ro_unit_summary_t *png_summary);
 
 /* The directory ro_periodic_plan left, in the level form the call above reads: host arithmetic.  Entry d of level_dir
  * describes dir[d]: RO_PERIODIC_WRITTEN becomes {offset / 4, bytes = naxis1 rows, naxis2 = rows, naxis1, RO_UNIT_WRITTEN}

@@ -271,6 +271,10 @@ _EXPORTS = {
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ro_levels_png_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p]),
+    "ro_stft_levels_png_deflate_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ro_levels_png_deflate_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_void_p]),
     "ro_periodic_level_dir": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -785,12 +789,7 @@ def png_bytes(naxis1, naxis2):
     return n
 
 
-def levels_png_host(level_dir, level_summary, levels, png_room, dir_capacity=None):
-    """The preview files of one level directory over host memory -- ro_levels_png_host.  level_dir: FITS_UNIT_DTYPE entries in
-    level terms and level_summary: the UNIT_SUMMARY_DTYPE of the call that wrote them (snapshot_levels_host, or
-    periodic_level_dir); levels: uint8; png_room: the room in bytes; dir_capacity: entries of level_dir to look at (None: all).
-    Returns (directory, files, summary): one FITS_UNIT_DTYPE entry per level entry (offset into the files, a multiple of 16;
-    bytes: the file's exact size), the bytes of the files in use, a UNIT_SUMMARY_DTYPE scalar."""
+def _levels_png_host(call, level_dir, level_summary, levels, png_room, dir_capacity):
     level_dir = np.ascontiguousarray(level_dir)
     level_summary = np.ascontiguousarray(level_summary).reshape(-1)
     if level_dir.dtype != FITS_UNIT_DTYPE or level_dir.ndim != 1 or level_summary.dtype != UNIT_SUMMARY_DTYPE or level_summary.size < 1:
@@ -803,9 +802,26 @@ def levels_png_host(level_dir, level_summary, levels, png_room, dir_capacity=Non
     png = np.zeros(max(png_room, 1), np.uint8)
     out = np.zeros(1, UNIT_SUMMARY_DTYPE)
     p = lambda a: C.c_void_p(a.ctypes.data)
-    _check(library().ro_levels_png_host(p(level_dir) if dcap else None, dcap, p(level_summary), p(levels) if levels.size else None,
-                                        levels.size, p(png_dir), p(png) if png_room > 0 else None, png_room, p(out)))
+    _check(call(p(level_dir) if dcap else None, dcap, p(level_summary), p(levels) if levels.size else None,
+                levels.size, p(png_dir), p(png) if png_room > 0 else None, png_room, p(out)))
     return png_dir[:int(out["entries"][0])], png[:int(out["units_bytes"][0])], out[0]
+
+
+def levels_png_host(level_dir, level_summary, levels, png_room, dir_capacity=None):
+    """The preview files of one level directory over host memory -- ro_levels_png_host.  level_dir: FITS_UNIT_DTYPE entries in
+    level terms and level_summary: the UNIT_SUMMARY_DTYPE of the call that wrote them (snapshot_levels_host, or
+    periodic_level_dir); levels: uint8; png_room: the room in bytes; dir_capacity: entries of level_dir to look at (None: all).
+    Returns (directory, files, summary): one FITS_UNIT_DTYPE entry per level entry (offset into the files, a multiple of 16;
+    bytes: the file's exact size), the bytes of the files in use, a UNIT_SUMMARY_DTYPE scalar."""
+    return _levels_png_host(library().ro_levels_png_host, level_dir, level_summary, levels, png_room, dir_capacity)
+
+
+def levels_png_deflate_host(level_dir, level_summary, levels, png_room, dir_capacity=None):
+    """The compressed preview files of one level directory over host memory -- ro_levels_png_deflate_host: the arguments and
+    the return of levels_png_host, the files' deflate blocks Huffman coded where that is shorter, so a file's bytes depend on
+    its levels and are at most png_bytes(naxis1, naxis2).  png_room = 0 is the sizing call: the summary's needed_bytes is the
+    room that holds every writable file."""
+    return _levels_png_host(library().ro_levels_png_deflate_host, level_dir, level_summary, levels, png_room, dir_capacity)
 
 
 def periodic_level_dir(directory):
@@ -1069,6 +1085,15 @@ class Stft:
         _check(library().ro_stft_levels_png_resident(self._h, _ptr(d_level_dir), dir_capacity, _ptr(d_level_summary),
                                                      _ptr(d_levels), levels_bytes, _ptr(d_png_dir), _ptr(d_png), png_bytes,
                                                      _ptr(d_png_summary), _ptr(stream)))
+
+    def levels_png_deflate_resident(self, d_level_dir, dir_capacity, d_level_summary, d_levels, levels_bytes, d_png_dir, d_png,
+                                    png_bytes, d_png_summary, stream=None):
+        """levels_png_resident with the files' deflate blocks Huffman coded where that is shorter --
+        ro_stft_levels_png_deflate_resident.  The files are packed by their actual sizes, at most png_bytes(naxis1, naxis2)
+        each; d_png = None with png_bytes = 0 is the sizing call (d_png_summary's needed_bytes)"""
+        _check(library().ro_stft_levels_png_deflate_resident(self._h, _ptr(d_level_dir), dir_capacity, _ptr(d_level_summary),
+                                                             _ptr(d_levels), levels_bytes, _ptr(d_png_dir), _ptr(d_png),
+                                                             png_bytes, _ptr(d_png_summary), _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

@@ -14,6 +14,7 @@
 //                        their host twins
 //   ro_png.cpp           the level images as complete PNG files (ro_png.hip), their host twin, and a periodic plan's
 //                        directory in level form
+//   ro_png_deflate.cpp   the same files with Huffman-coded deflate blocks (ro_png_deflate.hip), and their host twin
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
@@ -47,6 +48,7 @@
 #include "ro_periodic.h"
 #include "ro_levels.h"
 #include "ro_png.h"
+#include "ro_png_deflate.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -286,6 +288,9 @@ struct ro_stft {
     // preview files (ro_stft_levels_png_resident): the plan and the stored blocks' checksum parts of one call (ro_png.h);
     // grows with dir_capacity and with png_bytes
     DeviceBlock<char> d_png_scratch;
+    // compressed preview files (ro_stft_levels_png_deflate_resident): the plan, every block's size, code table and checksum
+    // parts of one call (ro_png_deflate.h); grows with dir_capacity and with levels_bytes
+    DeviceBlock<char> d_png_deflate_scratch;
     int cus = 0;                               // the device's compute units (device_cus; 0: not asked for yet)
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
@@ -356,6 +361,13 @@ int launch_spectra_big(ro_stft *h, const void *d_iq, int format, int64_t first_r
 // ---- ro_snapshots.cpp
 // what every call that takes a row ring asks of it (null: refused too), as a refusal in the name of `who`
 int ring_check(const char *who, const ro_row_ring_t *ring);
+
+// ---- ro_png.cpp
+// what the preview files' calls ask of their arguments, as a refusal in the name of `who`; d: "d_" where the arrays are the
+// device's; aligned: the device's files start at multiples of 16 bytes of an aligned buffer
+int png_check(const char *who, const char *d, bool aligned, const ro_fits_unit_t *level_dir, int64_t dir_capacity,
+              const ro_unit_summary_t *level_summary, const void *levels, int64_t levels_bytes, const ro_fits_unit_t *png_dir,
+              const void *png, int64_t png_bytes, const ro_unit_summary_t *png_summary);
 
 // ---- ro_units.cpp
 // the argument names a refusal speaks of: the units' calls and the levels' calls (ro_levels.cpp) ask the same of them

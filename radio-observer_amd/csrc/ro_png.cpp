@@ -8,11 +8,7 @@ using namespace ro::host;
 
 static_assert(RO_PNG_ALIGN == 16 && sizeof(ro_fits_unit_t) == 32, "the files' alignment and their directory are ABI");
 
-namespace {
-
-constexpr ro::PngTables TABLES = ro::make_png_tables();
-
-int png_check(const char *who, const char *d, bool aligned, const ro_fits_unit_t *level_dir, int64_t dir_capacity,
+int ro::host::png_check(const char *who, const char *d, bool aligned, const ro_fits_unit_t *level_dir, int64_t dir_capacity,
               const ro_unit_summary_t *level_summary, const void *levels, int64_t levels_bytes, const ro_fits_unit_t *png_dir,
               const void *png, int64_t png_bytes, const ro_unit_summary_t *png_summary)
 {
@@ -37,6 +33,10 @@ int png_check(const char *who, const char *d, bool aligned, const ro_fits_unit_t
     }
     return RO_OK;
 }
+
+namespace {
+
+constexpr ro::PngTables TABLES = ro::make_png_tables();
 
 uint32_t crc_bytes(uint32_t c, const unsigned char *p, int64_t n)
 {
