@@ -12,9 +12,12 @@
 //                        and the host twin
 //   ro_levels.cpp        the grey-level previews of the event snapshots and of the periodic snapshots (ro_levels.hip), and
 //                        their host twins
-//   ro_png.cpp           the level images as complete PNG files (ro_png.hip), their host twin, and a periodic plan's
-//                        directory in level form
-//   ro_png_deflate.cpp   the same files with Huffman-coded deflate blocks (ro_png_deflate.hip), and their host twin
+//   ro_png.cpp           the level images as complete PNG files (ro_png.hip), the one file writer of the host and the host
+//                        twins of both kinds of file over it, and a periodic plan's directory in level form
+//   ro_png_deflate.cpp   the same files with Huffman-coded deflate blocks (ro_png_deflate.hip), and a block's code and its
+//                        bytes on the host, in either form
+// Said once, here: pack_walk, the walk of every host twin that packs a source directory into a buffer (the units, the level
+// images, both kinds of file), and scratch_for (ro_stft_capi.cpp), the prelude of every plan-then-copy call.
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
 // There is no CPU compute path in any of them: rows only ever come out of the HIP kernels.
 #pragma once
@@ -355,6 +358,9 @@ int ensure_ln_part(ro_stft *h, int64_t rows);
 int grow_scratch(DeviceBlock<char> &block, size_t need);
 // the device's compute units, asked for once per handle: they size those calls' copy grids; the handle's device is current
 int device_cus(ro_stft *h, int *cus);
+// the prelude of a plan-then-copy call, in this order: the handle's device made current, its compute units, `block` grown to
+// `need` bytes
+int scratch_for(ro_stft *h, DeviceBlock<char> &block, size_t need, int *cus);
 int launch_spectra_big(ro_stft *h, const void *d_iq, int format, int64_t first_row, int64_t rows, float2 *d_out,
                        int64_t out_stride, hipStream_t s);
 
@@ -368,6 +374,23 @@ int ring_check(const char *who, const ro_row_ring_t *ring);
 int png_check(const char *who, const char *d, bool aligned, const ro_fits_unit_t *level_dir, int64_t dir_capacity,
               const ro_unit_summary_t *level_summary, const void *levels, int64_t levels_bytes, const ro_fits_unit_t *png_dir,
               const void *png, int64_t png_bytes, const ro_unit_summary_t *png_summary);
+// the two resident calls' arguments as the kernels take them (ro::PngArgs but the scratch)
+void png_fill_args(ro::PngArgs &a, const ro_fits_unit_t *level_dir, int64_t dir_capacity, const ro_unit_summary_t *level_summary,
+                   const void *levels, int64_t levels_bytes, ro_fits_unit_t *png_dir, void *png, int64_t png_bytes,
+                   ro_unit_summary_t *png_summary);
+
+// ---- ro_png_deflate.cpp
+// a deflate block on the host: its bytes in the stream in the shorter form, and where that is the Huffman form every
+// symbol's length and its code as the stream takes it
+struct DeflateCode {
+    int64_t bytes;
+    bool huffman;
+    uint8_t length[ro::DEFLATE_SYMS];
+    uint16_t reversed[ro::DEFLATE_SYMS];
+};
+DeflateCode deflate_code(const unsigned char *raw, int64_t len, bool last);
+// `len` raw bytes as one block at `out`, in the form `code` has chosen, stored for a null one; the bytes written
+int64_t deflate_write_block(const unsigned char *raw, int64_t len, bool last, const DeflateCode *code, unsigned char *out);
 
 // ---- ro_units.cpp
 // the argument names a refusal speaks of: the units' calls and the levels' calls (ro_levels.cpp) ask the same of them
@@ -381,45 +404,63 @@ int units_check(const char *who, const char *d, const UnitNames &names, bool raw
                 int64_t dir_capacity, const void *summary, const float *arena, int64_t arena_floats, int32_t cols,
                 const ro_band_window_t *slot_windows, const ro_fits_unit_t *unit_dir, const void *units, int64_t units_bytes,
                 const ro_unit_summary_t *unit_summary);
-// The twins' walk over n entries.  want(d): what source entry d asks for (ro_units.h).  A written entry takes `elem` bytes
-// per pixel in blocks of `block` bytes -- 4 and 2880 for a unit, 1 and 720 for a level image: the same number of blocks --
-// and emit(d, w, dst) writes its elem x naxis1 x naxis2 data bytes; the padding is zeroed here
+// The walk of every host twin that packs a source directory into a buffer: ro_snapshot_units_host, ro_raw_units_host,
+// ro_snapshot_levels_host, ro_levels_png_host and ro_levels_png_deflate_host.  want(d) says what source entry d asks for:
+// its status (RO_UNIT_SKIPPED, RO_UNIT_INVALID, or RO_UNIT_WRITTEN for a writable one), and for a writable one its shape,
+// its data bytes and its room, a multiple of the call's block or alignment: 2880 bytes per block of a unit, 720 per block
+// of a level image, png_room(bytes) for a file.  An entry is placed when the rooms up to and including its own are at most
+// buf_bytes; then emit(d, dst) writes its `bytes` bytes, before the next want, and the rest of its room is zeroed here.
+// The device plans of the units and the levels count in blocks: first_b + blocks <= buf_bytes / block, with the quotient
+// rounded down.  For integers that are not negative that is (first_b + blocks) block <= buf_bytes, the rule in bytes.
+// A room is below 2^62 -- a unit's is four times floats that lie in real memory, a file's is below 2^32 -- and so is the sum
+// of the at most 2^24 rooms of a directory over real memory: first + room does not overflow
+struct WalkWant {
+    int32_t status;
+    int32_t naxis1;
+    int64_t naxis2;
+    int64_t bytes;
+    int64_t room;
+};
 template <class Want, class Emit>
-void units_walk(int64_t n, Want want, int64_t elem, int64_t block, Emit emit, ro_fits_unit_t *unit_dir, void *units,
-                int64_t units_bytes, ro_unit_summary_t *unit_summary)
+void pack_walk(int64_t n, Want want, Emit emit, ro_fits_unit_t *dir, void *buf, int64_t buf_bytes, ro_unit_summary_t *summary)
 {
     ro_unit_summary_t sum{};
     sum.entries = n;
-    const int64_t room = units_bytes / block;
-    int64_t first_b = 0;                         // blocks of every writable entry so far, fitting or not
+    int64_t first = 0;                           // rooms of every writable entry so far, fitting or not
     for (int64_t d = 0; d < n; ++d) {
-        const ro::UnitWant w = want(d);
+        const WalkWant w = want(d);
         ro_fits_unit_t out{};
         out.status = w.status;
         if (w.status == RO_UNIT_SKIPPED) sum.skipped += 1;
         else if (w.status == RO_UNIT_INVALID) sum.invalid += 1;
         else {
-            const int64_t blocks = ro::unit_blocks(w.naxis1, w.naxis2);
-            out.bytes = elem * (int64_t)w.naxis1 * w.naxis2;
+            out.bytes = w.bytes;
             out.naxis2 = w.naxis2;
             out.naxis1 = w.naxis1;
-            if (first_b + blocks <= room) {
-                out.offset = first_b * block;
-                unsigned char *dst = static_cast<unsigned char *>(units) + out.offset;
-                emit(d, w, dst);
-                std::memset(dst + out.bytes, 0, (size_t)(blocks * block - out.bytes));
+            if (first + w.room <= buf_bytes) {
+                out.offset = first;
+                unsigned char *dst = static_cast<unsigned char *>(buf) + first;
+                emit(d, dst);
+                std::memset(dst + w.bytes, 0, (size_t)(w.room - w.bytes));
                 sum.written += 1;
-                sum.units_bytes = (first_b + blocks) * block;
+                sum.units_bytes = first + w.room;
             } else {
                 out.status = RO_UNIT_NO_ROOM;
                 sum.no_room += 1;
             }
-            first_b += blocks;
+            first += w.room;
         }
-        unit_dir[d] = out;
+        dir[d] = out;
     }
-    sum.needed_bytes = first_b * block;
-    *unit_summary = sum;
+    sum.needed_bytes = first;
+    *summary = sum;
+}
+// what a unit's or a level image's entry asks of the walk: `elem` bytes per pixel in blocks of `block` bytes -- 4 and 2880
+// for a unit, 1 and 720 for a level image: the same number of blocks
+inline WalkWant walk_want(const ro::UnitWant &w, int64_t elem, int64_t block)
+{
+    if (w.status != RO_UNIT_WRITTEN) return WalkWant{w.status, 0, 0, 0, 0};
+    return WalkWant{w.status, w.naxis1, w.naxis2, elem * (int64_t)w.naxis1 * w.naxis2, ro::unit_blocks(w.naxis1, w.naxis2) * block};
 }
 // the entries of a source directory: n = min(max(resolved, 0), dir_capacity)
 inline int64_t entries_of(int64_t resolved, int64_t dir_capacity) { return std::min(std::max<int64_t>(resolved, 0), dir_capacity); }

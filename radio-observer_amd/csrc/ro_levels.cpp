@@ -77,10 +77,8 @@ extern "C" int ro_stft_snapshot_levels_resident(ro_stft_t *h, const ro_snapshot_
     a.levels = static_cast<char *>(d_levels);
     a.levels_bytes = levels_bytes;
     a.level_summary = d_level_summary;
-    HIP_TRY(hipSetDevice(h->device));
     int cus = 0;
-    if ((rc = device_cus(h, &cus)) != RO_OK) return rc;
-    if ((rc = grow_scratch(h->d_levels_scratch[0], ro::snapshot_levels_scratch_bytes(dir_capacity, levels_bytes))) != RO_OK) return rc;
+    if ((rc = scratch_for(h, h->d_levels_scratch[0], ro::snapshot_levels_scratch_bytes(dir_capacity, levels_bytes), &cus)) != RO_OK) return rc;
     ro::snapshot_levels_scratch_layout(a, h->d_levels_scratch[0]);
     HIP_TRY(ro::launch_snapshot_levels(a, cus, (hipStream_t)stream));
     return RO_OK;
@@ -98,11 +96,12 @@ extern "C" int ro_snapshot_levels_host(const ro_snapshot_t *dir, int64_t dir_cap
     if (dir_capacity > 0 && !ranges) return fail(RO_ERR_INVALID, "%s: null ranges with dir_capacity %lld", who, (long long)dir_capacity);
     const int64_t n = entries_of(snap_summary->resolved, dir_capacity);
     for (int64_t d = 0; d < n; ++d) ranges[d] = ro_level_range_t{0.f, 0.f};
-    units_walk(n, [&](int64_t d) { return unit_want_snapshot(dir[d], cols, arena_floats, slot_windows); }, 1, RO_LEVEL_BLOCK,
-               [&](int64_t d, const ro::UnitWant &w, unsigned char *dst) {
-                   image_levels(arena, (int64_t)w.naxis1 * w.naxis2,
-                                [&](int64_t i) { return w.first + i / w.naxis1 * cols + i % w.naxis1; }, &ranges[d], dst);
-               }, level_dir, levels, levels_bytes, level_summary);
+    auto want = [&](int64_t d) { return unit_want_snapshot(dir[d], cols, arena_floats, slot_windows); };
+    pack_walk(n, [&](int64_t d) { return walk_want(want(d), 1, RO_LEVEL_BLOCK); }, [&](int64_t d, unsigned char *dst) {
+        const ro::UnitWant w = want(d);
+        image_levels(arena, (int64_t)w.naxis1 * w.naxis2, [&](int64_t i) { return w.first + i / w.naxis1 * cols + i % w.naxis1; },
+                     &ranges[d], dst);
+    }, level_dir, levels, levels_bytes, level_summary);
     return RO_OK;
 }
 
@@ -120,10 +119,8 @@ extern "C" int ro_stft_periodic_levels_resident(ro_stft_t *h, const ro_row_ring_
     if (!d_ranges) return fail(RO_ERR_INVALID, "%s: null d_ranges with a WRITTEN entry", who);
     a.ranges = d_ranges;
     a.levels = static_cast<char *>(d_levels);
-    HIP_TRY(hipSetDevice(h->device));
     int cus = 0;
-    if ((rc = device_cus(h, &cus)) != RO_OK) return rc;
-    if ((rc = grow_scratch(h->d_levels_scratch[1], (size_t)a.p.blocks * sizeof(ro::LevelKeys))) != RO_OK) return rc;
+    if ((rc = scratch_for(h, h->d_levels_scratch[1], (size_t)a.p.blocks * sizeof(ro::LevelKeys), &cus)) != RO_OK) return rc;
     a.keys = reinterpret_cast<ro::LevelKeys *>(static_cast<char *>(h->d_levels_scratch[1]));
     HIP_TRY(ro::launch_periodic_levels(a, cus, (hipStream_t)stream));
     return RO_OK;

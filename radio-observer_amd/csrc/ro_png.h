@@ -217,4 +217,19 @@ void png_scratch_layout(PngArgs &a, void *scratch);
 // the plan, the blocks and the finish on `s`: three launches; cus: the device's compute units
 hipError_t launch_levels_png(const PngArgs &a, int cus, hipStream_t s);
 
+// what the launchers of both kinds of file (ro_png.hip, ro_png_deflate.hip) ask of the arguments they share, but max_blocks
+inline bool png_args_valid(const PngArgs &a)
+{
+    return a.dir_capacity >= 0 && a.dir_capacity <= PNG_MAX_ENTRIES && (a.dir_capacity == 0 || a.level_dir) && a.entries &&
+           a.levels_bytes >= 0 && (a.levels_bytes == 0 || a.levels) && a.png_dir && a.png_bytes >= 0 && (a.png_bytes == 0 || a.png) &&
+           ((uintptr_t)a.png & (RO_PNG_ALIGN - 1)) == 0 && a.summary && a.head && a.first_block && a.parts;
+}
+// ... and their grids: of the `most` workgroups of a copy (copy_grid, ro_pack_plan.h) no more than there are items for them,
+// `per_group` to a workgroup
+inline unsigned png_grid_for(unsigned most, int64_t items, int per_group)
+{
+    const int64_t need = (items + per_group - 1) / per_group;
+    return (unsigned)(need < 1 ? 1 : need < (int64_t)most ? need : (int64_t)most);
+}
+
 }  // namespace ro

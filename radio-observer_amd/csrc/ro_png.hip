@@ -18,7 +18,8 @@
 //                      block to the end of the chunk.  Block 0's workgroup writes the file's first 48 bytes too
 //   png_finish_kernel  a wave takes a file: adds its blocks' parts, writes the Adler-32, the IDAT CRC, IEND and the zeros
 //                      up to the next multiple of 16
-// Every level byte is read once and a byte is written per raw byte.
+// Every level byte is read once and a byte is written per raw byte.  What these kernels and ro_png_deflate.hip's do the same
+// way once per entry or per block is ro_png_crc_device.h's; the launchers' common checks and grids are ro_png.h's.
 #include "ro_pack_plan.h"
 #include "ro_png.h"
 #include "ro_png_crc_device.h"
@@ -52,9 +53,7 @@ __global__ __launch_bounds__(T) void png_plan_kernel(PngArgs a)
     for (int64_t t0 = 0; t0 < n; t0 += T) {
         const int64_t c = t0 + threadIdx.x;
         // (lanes past the last entry read it once more and take no part: no guarded load of a struct)
-        const int64_t *e = reinterpret_cast<const int64_t *>(a.level_dir + (c < n ? c : n - 1));
-        const int64_t e3 = e[3];
-        const PngWant w = png_want(e[0], e[1], e[2], (int32_t)(uint32_t)e3, (int32_t)(uint32_t)((uint64_t)e3 >> 32), a.levels_bytes);
+        const PngWant w = png_want_entry(a.level_dir, c < n ? c : n - 1, a.levels_bytes);
         const bool live = c < n;
         const bool writable = live && w.status == RO_UNIT_WRITTEN;
         const int64_t take[2] = {writable ? png_room(w.bytes) : 0, writable ? w.blocks : 0};
@@ -84,16 +83,7 @@ __global__ __launch_bounds__(T) void png_plan_kernel(PngArgs a)
         block_base += scan.total[1];
     }
     if (threadIdx.x == 0) {
-        ro_unit_summary_t sum;
-        sum.entries = n;
-        sum.written = written;
-        sum.skipped = skipped;
-        sum.no_room = no_room;
-        sum.invalid = invalid;
-        sum.units_bytes = used;
-        sum.needed_bytes = byte_base;
-        sum.reserved = 0;
-        *a.summary = sum;
+        png_store_summary(a.summary, n, written, skipped, no_room, invalid, used, byte_base);
         PngPlanHead head;
         head.entries = n;
         head.blocks = used_blocks < a.max_blocks ? used_blocks : a.max_blocks;     // (files side by side have no more)
@@ -207,13 +197,8 @@ __global__ __launch_bounds__(T) void png_blocks_kernel(PngArgs a)
             const uint32_t power = wave_xpow8(tab.x2n, lane < 32 ? behind : behind + len, lane);
             const uint32_t power_block = (uint32_t)__shfl((int)power, 32);
             if (lane == 0) {
-                uint32_t c = 0u, A = 0u, B = 0u;
-#pragma unroll
-                for (int v = 0; v < PLAN_WAVES; ++v) {
-                    c ^= red[turn][v][0];
-                    A += red[turn][v][1];
-                    B += red[turn][v][2];
-                }
+                uint32_t c, A, B;
+                png_fold(red[turn], c, A, B);
                 // the bytes behind the last whole word; a block that is not the last has three, and the word they
                 // share with the next block's first header byte is written here
                 unsigned word = 0u;
@@ -234,12 +219,7 @@ __global__ __launch_bounds__(T) void png_blocks_kernel(PngArgs a)
                     for (int i = 0; i < 5; ++i) pre = crc_byte(tab, pre, png_block_header_byte(i, last, len));
                     *reinterpret_cast<unsigned *>(block + 1) = len | ((~len & 0xffffu) << 16);               // LEN, ~LEN
                 }
-                PngPart part;
-                part.crc = crc_mul(pre, power_block) ^ crc_mul(c, power);
-                part.a = A % ADLER_MOD;
-                part.b = (uint32_t)((B % ADLER_MOD + (uint64_t)((f.raw - r0 - len) % ADLER_MOD) * part.a) % ADLER_MOD);
-                part.reserved = 0u;
-                a.parts[b] = part;
+                a.parts[b] = png_part(c, A, B, pre, power, power_block, f.raw - r0 - len);
             }
         } else if (t == 64 && k == 0) {
             // the file's head, by one lane of another wave: 48 bytes, most of them constants
@@ -283,13 +263,6 @@ __global__ __launch_bounds__(64 * COPY_WAVES) void png_finish_kernel(PngArgs a)
     }
 }
 
-// no more workgroups than there are items for them
-unsigned grid_for(int cus, int64_t items, int per_group)
-{
-    const int64_t need = (items + per_group - 1) / per_group;
-    return (unsigned)std::max<int64_t>(std::min<int64_t>(copy_grid(cus), need), 1);
-}
-
 }  // namespace
 
 size_t png_scratch_bytes(int64_t dir_capacity, int64_t png_bytes)
@@ -309,15 +282,11 @@ void png_scratch_layout(PngArgs &a, void *scratch)
 
 hipError_t launch_levels_png(const PngArgs &a, int cus, hipStream_t s)
 {
-    if (a.dir_capacity < 0 || a.dir_capacity > PNG_MAX_ENTRIES || (a.dir_capacity > 0 && !a.level_dir) || !a.entries ||
-        a.levels_bytes < 0 || (a.levels_bytes > 0 && !a.levels) || !a.png_dir || a.png_bytes < 0 || (a.png_bytes > 0 && !a.png) ||
-        ((uintptr_t)a.png & (RO_PNG_ALIGN - 1)) != 0 || !a.summary || !a.head || !a.first_block || !a.parts ||
-        a.max_blocks != png_max_blocks(a.dir_capacity, a.png_bytes))
-        return hipErrorInvalidValue;
+    if (!png_args_valid(a) || a.max_blocks != png_max_blocks(a.dir_capacity, a.png_bytes)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(png_plan_kernel, dim3(1), dim3(T), 0, s, a);
     // the work is known on the device only, but it is at most the blocks of the room and the entries of the directory
-    hipLaunchKernelGGL(png_blocks_kernel, dim3(grid_for(cus, a.max_blocks, 1)), dim3(T), 0, s, a);
-    hipLaunchKernelGGL(png_finish_kernel, dim3(grid_for(cus, a.dir_capacity, COPY_WAVES)), dim3(64 * COPY_WAVES), 0, s, a);
+    hipLaunchKernelGGL(png_blocks_kernel, dim3(png_grid_for(copy_grid(cus), a.max_blocks, 1)), dim3(T), 0, s, a);
+    hipLaunchKernelGGL(png_finish_kernel, dim3(png_grid_for(copy_grid(cus), a.dir_capacity, COPY_WAVES)), dim3(64 * COPY_WAVES), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1,5 +1,8 @@
 // ro_png_crc_device.h -- device helpers of the preview files' kernels (ro_png.hip, ro_png_deflate.hip): the raw bytes of an
-// image of scanlines, the CRC-32 steps over the tables of ro_png.h, and the wave's sums.  Device code only.
+// image of scanlines, the CRC-32 steps over the tables of ro_png.h, the wave's sums, and what both files' kernels do the
+// same way once per entry or per block: the read of a level entry, the store of the summary, the fold of the waves' sums and
+// a block's part of the file's checksums.  (The two finish kernels keep their bodies: as a shared function the same lines
+// cost png_finish_kernel one more SGPR, profiles/png_refactor.txt.)  Device code only.
 #pragma once
 
 #include "ro_pack_plan.h"
@@ -74,6 +77,59 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x)
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) x += (uint32_t)__shfl_xor((int)x, off);
     return x;
+}
+
+// ---- what the two files' kernels do once per entry, per block or per file, outside every loop over bytes
+
+// what level entry d asks for: the entry read as its four words (no guarded load of a struct)
+__device__ __forceinline__ PngWant png_want_entry(const ro_fits_unit_t *level_dir, int64_t d, int64_t levels_bytes)
+{
+    const int64_t *e = reinterpret_cast<const int64_t *>(level_dir + d);
+    const int64_t e3 = e[3];
+    return png_want(e[0], e[1], e[2], (int32_t)(uint32_t)e3, (int32_t)(uint32_t)((uint64_t)e3 >> 32), levels_bytes);
+}
+
+// the files' summary, stored by the one thread that calls this
+__device__ __forceinline__ void png_store_summary(ro_unit_summary_t *summary, int64_t entries, int64_t written, int64_t skipped,
+                                                  int64_t no_room, int64_t invalid, int64_t used, int64_t needed)
+{
+    ro_unit_summary_t sum;
+    sum.entries = entries;
+    sum.written = written;
+    sum.skipped = skipped;
+    sum.no_room = no_room;
+    sum.invalid = invalid;
+    sum.units_bytes = used;
+    sum.needed_bytes = needed;
+    sum.reserved = 0;
+    *summary = sum;
+}
+
+// the waves' sums of one block, as each wave's lane 0 left them in LDS, folded: the CRC state and the two Adler sums
+template <int N>
+__device__ __forceinline__ void png_fold(const uint32_t (&red)[PLAN_WAVES][N], uint32_t &c, uint32_t &A, uint32_t &B)
+{
+    c = A = B = 0u;
+#pragma unroll
+    for (int v = 0; v < PLAN_WAVES; ++v) {
+        c ^= red[v][0];
+        A += red[v][1];
+        B += red[v][2];
+    }
+}
+
+// The part of one block (PngPart): c the state over the block's bytes, pre the state over what stands in front of them in
+// the chunk, power and power_block x to 8 times the IDAT bytes behind the block and behind its first byte; A and B the
+// block's Adler sums, `raw_behind` the image's raw bytes behind the block
+__device__ __forceinline__ PngPart png_part(uint32_t c, uint32_t A, uint32_t B, uint32_t pre, uint32_t power, uint32_t power_block,
+                                            unsigned raw_behind)
+{
+    PngPart part;
+    part.crc = crc_mul(pre, power_block) ^ crc_mul(c, power);
+    part.a = A % ADLER_MOD;
+    part.b = (uint32_t)((B % ADLER_MOD + (uint64_t)(raw_behind % ADLER_MOD) * part.a) % ADLER_MOD);
+    part.reserved = 0u;
+    return part;
 }
 
 }  // namespace ro

@@ -2,7 +2,8 @@
 // directory as a complete PNG whose deflate blocks are dynamic-Huffman blocks of literals only, or stored ones where those
 // are not shorter (RFC 1951 3.2.2, 3.2.4, 3.2.7).  include/ro_stft.h states the file to the byte; this header has the
 // arithmetic of a block -- the code lengths from the sorted frequencies, the limit to 15 bits, the block's header bits and
-// its size -- shared by the kernels and the host twin, and what the host side needs to launch.  The file around the blocks,
+// its size -- shared by the kernels and the host's block coder (deflate_code, ro_png_deflate.cpp; the twin that walks the
+// directory is in ro_png.cpp), and what the host side needs to launch.  The file around the blocks,
 // the entry rule and the checksum constants are ro_png.h's.
 #pragma once
 

@@ -60,9 +60,7 @@ __global__ __launch_bounds__(T) void deflate_want_kernel(DeflateArgs a)
 #pragma unroll 1
     for (int64_t t0 = 0; t0 < n; t0 += T) {
         const int64_t c = t0 + threadIdx.x;
-        const int64_t *e = reinterpret_cast<const int64_t *>(a.p.level_dir + (c < n ? c : n - 1));
-        const int64_t e3 = e[3];
-        const PngWant w = png_want(e[0], e[1], e[2], (int32_t)(uint32_t)e3, (int32_t)(uint32_t)((uint64_t)e3 >> 32), a.p.levels_bytes);
+        const PngWant w = png_want_entry(a.p.level_dir, c < n ? c : n - 1, a.p.levels_bytes);
         const bool live = c < n;
         const bool valid = live && w.status == RO_UNIT_WRITTEN;
         const int64_t take[1] = {valid ? w.blocks : 0};
@@ -93,9 +91,8 @@ struct DeflateSource {
 
 __device__ __forceinline__ bool deflate_source(const DeflateArgs &a, int64_t d, DeflateSource &f)
 {
-    const int64_t *e = reinterpret_cast<const int64_t *>(a.p.level_dir + d);
-    const int64_t e3 = e[3], first = a.p.first_block[d];
-    const PngWant w = png_want(e[0], e[1], e[2], (int32_t)(uint32_t)e3, (int32_t)(uint32_t)((uint64_t)e3 >> 32), a.p.levels_bytes);
+    const int64_t first = a.p.first_block[d];
+    const PngWant w = png_want_entry(a.p.level_dir, d, a.p.levels_bytes);
     int64_t raw, blocks, idat;
     if (w.status != RO_UNIT_WRITTEN || !png_shape(w.naxis1, w.naxis2, &raw, &blocks, &idat) || first < 0 ||
         first > a.p.max_blocks || blocks > a.p.max_blocks - first)
@@ -298,18 +295,7 @@ __global__ __launch_bounds__(T) void deflate_place_kernel(DeflateArgs a)
         }
         byte_base += scan.total[0];
     }
-    if (threadIdx.x == 0) {
-        ro_unit_summary_t sum;
-        sum.entries = n;
-        sum.written = written;
-        sum.skipped = skipped;
-        sum.no_room = no_room;
-        sum.invalid = invalid;
-        sum.units_bytes = used;
-        sum.needed_bytes = byte_base;
-        sum.reserved = 0;
-        *a.p.summary = sum;
-    }
+    if (threadIdx.x == 0) png_store_summary(a.p.summary, n, written, skipped, no_room, invalid, used, byte_base);
 }
 
 // a written file as the place left it, checked once more against the buffers before anything of it is touched
@@ -487,24 +473,14 @@ __global__ __launch_bounds__(T) void deflate_emit_kernel(DeflateArgs a)
             const uint32_t power = wave_xpow8(tab.x2n, lane < 32 ? behind : behind + n, lane);
             const uint32_t power_block = (uint32_t)__shfl((int)power, 32);
             if (lane == 0) {
-                uint32_t c = 0u, A = 0u, B = 0u;
-#pragma unroll
-                for (int v = 0; v < PLAN_WAVES; ++v) {
-                    c ^= red[v][0];
-                    A += red[v][1];
-                    B += red[v][2];
-                }
+                uint32_t c, A, B;
+                png_fold(red, c, A, B);
                 for (unsigned q = 4u * full; q < np; ++q) c = crc_byte(tab, c, (stage[q >> 2] >> (8u * (q & 3u))) & 0xffu);
                 // what stands in front of block 0 in the chunk's CRC: the chunk type and 78 01
                 uint32_t pre = 0u;
                 if (it.k == 0)
                     for (int i = 37; i < (int)PNG_HEAD; ++i) pre = crc_byte(tab, pre, png_head_byte(i, 0u, 0u, 0u, 0u, false, 0u));
-                PngPart part;
-                part.crc = crc_mul(pre, power_block) ^ crc_mul(c, power);
-                part.a = A % ADLER_MOD;
-                part.b = (uint32_t)((B % ADLER_MOD + (uint64_t)((src.raw - it.r0 - len) % ADLER_MOD) * part.a) % ADLER_MOD);
-                part.reserved = 0u;
-                a.p.parts[b] = part;
+                a.p.parts[b] = png_part(c, A, B, pre, power, power_block, src.raw - it.r0 - len);
             }
         } else if (wave == 1 && it.k == 0) {
             // the file's head, by another wave: 43 bytes, most of them constants
@@ -549,13 +525,6 @@ __global__ __launch_bounds__(64 * COPY_WAVES) void deflate_finish_kernel(Deflate
     }
 }
 
-// no more workgroups than there are items for them
-unsigned grid_for(int cus, int64_t items, int per_group)
-{
-    const int64_t need = (items + per_group - 1) / per_group;
-    return (unsigned)std::max<int64_t>(std::min<int64_t>(copy_grid(cus), need), 1);
-}
-
 }  // namespace
 
 size_t deflate_scratch_bytes(int64_t dir_capacity, int64_t levels_bytes)
@@ -586,13 +555,11 @@ void deflate_scratch_layout(DeflateArgs &a, void *scratch)
 hipError_t launch_levels_png_deflate(const DeflateArgs &a, int cus, hipStream_t s)
 {
     const PngArgs &p = a.p;
-    if (p.dir_capacity < 0 || p.dir_capacity > PNG_MAX_ENTRIES || (p.dir_capacity > 0 && !p.level_dir) || !p.entries ||
-        p.levels_bytes < 0 || (p.levels_bytes > 0 && !p.levels) || !p.png_dir || p.png_bytes < 0 || (p.png_bytes > 0 && !p.png) ||
-        ((uintptr_t)p.png & (RO_PNG_ALIGN - 1)) != 0 || !p.summary || !p.head || !p.first_block || !p.parts || !a.stream ||
-        !a.blocks || !a.tables || p.max_blocks != deflate_max_blocks(p.dir_capacity, p.levels_bytes))
+    if (!png_args_valid(p) || !a.stream || !a.blocks || !a.tables || p.max_blocks != deflate_max_blocks(p.dir_capacity, p.levels_bytes))
         return hipErrorInvalidValue;
     // the work is known on the device only, but it is at most the blocks of the levels and the entries of the directory
-    const unsigned block_grid = grid_for(cus, p.max_blocks, 1), file_grid = grid_for(cus, p.dir_capacity, COPY_WAVES);
+    const unsigned block_grid = png_grid_for(copy_grid(cus), p.max_blocks, 1);
+    const unsigned file_grid = png_grid_for(copy_grid(cus), p.dir_capacity, COPY_WAVES);
     hipLaunchKernelGGL(deflate_want_kernel, dim3(1), dim3(T), 0, s, a);
     hipLaunchKernelGGL(deflate_measure_kernel, dim3(block_grid), dim3(T), 0, s, a);
     hipLaunchKernelGGL(deflate_sum_kernel, dim3(file_grid), dim3(64 * COPY_WAVES), 0, s, a);

@@ -86,10 +86,8 @@ extern "C" int ro_stft_raw_resident(ro_stft_t *h, const ro_snapshot_t *d_dir, in
     if (rc != RO_OK) return rc;
     int rate_r = 0;
     if ((rc = raw_rate(who, h->cfg.sample_rate, h->bins, h->cfg.overlap, &rate_r)) != RO_OK) return rc;
-    HIP_TRY(hipSetDevice(h->device));
     int cus = 0;
-    if ((rc = device_cus(h, &cus)) != RO_OK) return rc;
-    if ((rc = grow_scratch(h->d_raw_scratch, ro::raw_scratch_bytes(dir_capacity, pending_capacity))) != RO_OK) return rc;
+    if ((rc = scratch_for(h, h->d_raw_scratch, ro::raw_scratch_bytes(dir_capacity, pending_capacity), &cus)) != RO_OK) return rc;
     ro::RawArgs a{};
     a.dir = d_dir;
     a.snap_summary = d_snap_summary;

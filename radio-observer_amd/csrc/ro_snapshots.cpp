@@ -111,10 +111,8 @@ extern "C" int ro_stft_snapshots_resident(ro_stft_t *h, const ro_event_t *d_even
     int rc = snapshots_check(who, "d_", d_events, capacity, d_summary, slot_mask, snapshot_rows, ring, head_row, d_pending,
                                    d_pending_count, pending_capacity, d_dir, d_arena, arena_floats, d_snap_summary, &slots);
     if (rc != RO_OK) return rc;
-    HIP_TRY(hipSetDevice(h->device));
     int cus = 0;
-    if ((rc = device_cus(h, &cus)) != RO_OK) return rc;
-    if ((rc = grow_scratch(h->d_snap_scratch, ro::snap_scratch_bytes(slots, capacity, pending_capacity))) != RO_OK) return rc;
+    if ((rc = scratch_for(h, h->d_snap_scratch, ro::snap_scratch_bytes(slots, capacity, pending_capacity), &cus)) != RO_OK) return rc;
     ro::SnapArgs a{};
     a.events = d_events;
     a.summary = d_summary;

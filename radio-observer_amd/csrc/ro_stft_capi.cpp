@@ -1,6 +1,8 @@
 // ro_stft_capi.cpp -- the handle of the C ABI in include/ro_stft.h: create / destroy, the transform launches of every plan,
-// the resident entry points (rows, spectra, scan, ln tile, timing).  Owns the window / twiddle tables in HBM.  The rest of
-// the ABI: ro_abi_helpers.cpp, ro_exchange.cpp, ro_stream.cpp, ro_czt.cpp (ro_host.h lists who has what).
+// the resident entry points (rows, spectra, scan, ln tile, timing), and scratch_for, the prelude of the plan-then-copy calls.
+// Owns the window / twiddle tables in HBM.  The rest of the ABI: ro_abi_helpers.cpp, ro_exchange.cpp, ro_stream.cpp,
+// ro_czt.cpp, and a file per plan-then-copy feature: ro_snapshots.cpp, ro_raw.cpp, ro_units.cpp, ro_periodic.cpp,
+// ro_levels.cpp, ro_png.cpp, ro_png_deflate.cpp (ro_host.h lists who has what).
 #include "ro_host.h"
 
 using namespace ro::host;
@@ -356,6 +358,13 @@ int device_cus(ro_stft *h, int *cus)
     if (h->cus == 0) HIP_TRY(hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device));
     *cus = h->cus;
     return RO_OK;
+}
+
+int scratch_for(ro_stft *h, DeviceBlock<char> &block, size_t need, int *cus)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    const int rc = device_cus(h, cus);
+    return rc != RO_OK ? rc : grow_scratch(block, need);
 }
 
 // complex spectra of rows [first_row, +rows) of a large size (bins = dec x 32768), bin k at element k of each row:

@@ -82,30 +82,37 @@ const UnitNames UNITS = {"unit_dir", "units", "units_bytes", "unit_summary"};
 
 int units_launch(ro_stft_t *h, ro::UnitsArgs &a, int kind, void *stream)
 {
-    HIP_TRY(hipSetDevice(h->device));
-    int cus = 0, rc = device_cus(h, &cus);
-    if (rc != RO_OK) return rc;
     // one block per kind: the images' call and the raw runs' call of a chunk may be in flight on two streams
-    if ((rc = grow_scratch(h->d_units_scratch[kind], ro::units_scratch_bytes(a.dir_capacity))) != RO_OK) return rc;
+    int cus = 0;
+    const int rc = scratch_for(h, h->d_units_scratch[kind], ro::units_scratch_bytes(a.dir_capacity), &cus);
+    if (rc != RO_OK) return rc;
     ro::units_scratch_layout(a, h->d_units_scratch[kind]);
     HIP_TRY(ro::launch_units(a, kind, cus, (hipStream_t)stream));
     return RO_OK;
 }
 
 // the unit of a written entry, float by float: the four bytes of arena float first + r stride + c, reversed
-auto swapped_floats(const float *arena, int64_t stride)
+void swapped_floats(const float *arena, int64_t stride, const ro::UnitWant &w, unsigned char *dst)
 {
-    return [=](int64_t, const ro::UnitWant &w, unsigned char *dst) {
-        const unsigned char *src = reinterpret_cast<const unsigned char *>(arena);
-        for (int64_t r = 0; r < w.naxis2; ++r)
-            for (int64_t c = 0; c < w.naxis1; ++c, dst += 4) {
-                const unsigned char *f = src + 4 * (w.first + r * stride + c);
-                dst[0] = f[3];
-                dst[1] = f[2];
-                dst[2] = f[1];
-                dst[3] = f[0];
-            }
-    };
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(arena);
+    for (int64_t r = 0; r < w.naxis2; ++r)
+        for (int64_t c = 0; c < w.naxis1; ++c, dst += 4) {
+            const unsigned char *f = src + 4 * (w.first + r * stride + c);
+            dst[0] = f[3];
+            dst[1] = f[2];
+            dst[2] = f[1];
+            dst[3] = f[0];
+        }
+}
+
+// the twins: pack_walk over the call's entry rule, in units of 2880-byte blocks
+template <class Want>
+void units_walk(int64_t n, Want want, const float *arena, int64_t stride, ro_fits_unit_t *unit_dir, void *units,
+                int64_t units_bytes, ro_unit_summary_t *unit_summary)
+{
+    pack_walk(n, [&](int64_t d) { return walk_want(want(d), 4, RO_FITS_BLOCK); },
+              [&](int64_t d, unsigned char *dst) { swapped_floats(arena, stride, want(d), dst); }, unit_dir, units, units_bytes,
+              unit_summary);
 }
 
 }  // namespace
@@ -154,8 +161,8 @@ extern "C" int ro_snapshot_units_host(const ro_snapshot_t *dir, int64_t dir_capa
                                slot_windows, unit_dir, units, units_bytes, unit_summary);
     if (rc != RO_OK) return rc;
     units_walk(entries_of(snap_summary->resolved, dir_capacity),
-               [&](int64_t d) { return unit_want_snapshot(dir[d], cols, arena_floats, slot_windows); }, 4, RO_FITS_BLOCK,
-               swapped_floats(arena, cols), unit_dir, units, units_bytes, unit_summary);
+               [&](int64_t d) { return unit_want_snapshot(dir[d], cols, arena_floats, slot_windows); }, arena, cols, unit_dir,
+               units, units_bytes, unit_summary);
     return RO_OK;
 }
 
@@ -169,6 +176,6 @@ extern "C" int ro_raw_units_host(const ro_raw_capture_t *raw_dir, int64_t dir_ca
     units_walk(entries_of(raw_summary->resolved, dir_capacity), [&](int64_t d) {
         const ro_raw_capture_t &e = raw_dir[d];
         return ro::unit_want_raw(e.status, e.samples, e.offset, arena_floats);
-    }, 4, RO_FITS_BLOCK, swapped_floats(arena, 2), unit_dir, units, units_bytes, unit_summary);
+    }, arena, 2, unit_dir, units, units_bytes, unit_summary);
     return RO_OK;
 }
