@@ -986,7 +986,7 @@ int ro_periodic_levels_host(const ro_row_ring_t *ring, const ro_periodic_t *reco
  * What a station publishes of a preview is a .png.  One call turns every level image of a level directory into the bytes
  * of that file: 8 bit, grey, no interlace; a filter byte 0 in front of every scanline; the zlib stream in STORED deflate
  * blocks (no compression here: ro_stft_levels_png_deflate_resident below Huffman-codes the blocks; LZ77 and filter choice
- * stay out of scope, and so do fits2png's legend and axes and its --width); the Adler-32, the IDAT CRC-32, IEND.  A host downloads the files in use and makes one fwrite per file.
+ * stay out of scope, and so do fits2png's legend and axes; its --width is ro_stft_levels_resize_resident); the Adler-32, the IDAT CRC-32, IEND.  A host downloads the files in use and makes one fwrite per file.
  * For an image of W = naxis1 by H = naxis2 pixels: R = H (W + 1) raw bytes, the first FFT row first, in nblk =
  * ceil(R / 65535) stored blocks, every one but the last of exactly 65535 bytes:
  *   89 50 4E 47 0D 0A 1A 0A                                   the signature, 8 bytes
@@ -1051,7 +1051,7 @@ int ro_levels_png_host(const ro_fits_unit_t *level_dir, int64_t dir_capacity, co
  * The files above are as large as their pixels.  These two calls write the same files -- same signature, IHDR, one IDAT
  * with the zlib header 78 01 and the Adler-32 of the raw scanlines, IEND; filter byte 0; the raw bytes cut into blocks of
  * 65535, the last one shorter -- with every block in the shorter of two forms.  LZ77 matching and filter choice stay out of
- * scope, and so do fits2png's legend and axes and its --width.  Every block starts on a byte boundary of the stream.
+ * scope, and so do fits2png's legend and axes.  Every block starts on a byte boundary of the stream.
  *   STORED form    the five-byte header above (BFINAL, LEN, ~LEN) and the raw bytes: 5 + LEN bytes
  *   HUFFMAN form   BTYPE = 2 with literals only.  The alphabet is the 256 literals and end-of-block (symbol 256); f[0 ... 255]
  *                  are the frequencies of the block's raw bytes and f[256] = 1, so at least two symbols are used.
@@ -1113,6 +1113,99 @@ int ro_levels_png_deflate_host(const ro_fits_unit_t *level_dir, int64_t dir_capa
  * level_summary; an entry with an unknown status. */
 int ro_periodic_level_dir(const ro_periodic_entry_t *dir, int64_t entries, ro_fits_unit_t *level_dir,
                           ro_unit_summary_t *level_summary);
+
+/* ---- resized previews: fits2png's --width ----------------------------------------------
+ * What a station publishes of a WIDE preview is limited to about a thousand pixels of width: fits2png:510-517 is
+ * result.resize((width, int(height * ratio)), Image.ANTIALIAS), Pillow's Lanczos resize of an 8-bit image.  The calls here
+ * make that image from every level image of a level directory, byte for byte what Pillow makes, and leave it as a level
+ * directory again, so that ro_stft_levels_png_resident, ro_stft_levels_png_deflate_resident and their host twins read the
+ * result unchanged.  A chunk is ... the levels, ro_resize_plan, the upload of the plan, ro_stft_levels_resize_resident, a
+ * PNG call, one download.
+ * THE PLAN IS HOST ARITHMETIC, like ro_periodic_plan: the taps come from sin in double, and they only equal Pillow's when
+ * they come from the same C library -- a device sin differs in the last place often enough to flip a 22-bit tap, and then
+ * a pixel.  The device does integer work only, which is also what lets it agree with its host twin byte for byte.  So the
+ * shapes must be known on the host: for the periodic chain, where the wide images are, they are (ro_periodic_level_dir is
+ * host memory); for the event snapshots the host downloads the level directory and its summary first, 32 bytes an entry.
+ * Shape: an image is resized only when width < W = naxis1.  Then ratio = (double)width / (double)W, W' = width and
+ * H' = (int64)((double)H * ratio), truncated; H' can be 0.  Otherwise it keeps its shape.
+ * Coefficients of one axis (in -> out pixels, in != out), all in double: scale = in / out, fs = max(scale, 1), support =
+ * 3 fs, ss = 1 / fs, ksize = (int)ceil(support) * 2 + 1.  For output pixel xx: center = (xx + 0.5) scale; xmin =
+ * max((int)(center - support + 0.5), 0); xmax = min((int)(center + support + 0.5), in) - xmin; w[x] = L((x + xmin - center
+ * + 0.5) ss) for x < xmax, with L(t) = sinc(t) sinc(t / 3) for -3 <= t < 3 and 0 elsewhere, sinc(0) = 1 and sinc(t) =
+ * sin(pi t) / (pi t); ww = the sum of the w[x] in index order; k[x] = w[x] / ww; the fixed-point tap is (int)(k 2^22 + 0.5)
+ * for k >= 0 and (int)(k 2^22 - 0.5) otherwise.
+ * One pass: out = clamp((2^21 + sum over x < xmax of in[xmin + x] tap[x]) >> 22, 0, 255), the sum an int32, the shift
+ * arithmetic.  The horizontal pass (W -> W' on every row) is rounded to uint8 before the vertical one (H -> H') reads it;
+ * a pass whose two sizes are equal is skipped. */
+typedef struct ro_resize_info {    /* 64 bytes: the host scalars of one plan */
+    int64_t jobs;                  /* WRITTEN entries: one job each */
+    int64_t h_items, v_items;      /* work items of the two launches */
+    int64_t mid_bytes;             /* the intermediate images, W' x H bytes per job that runs both passes (handle scratch) */
+    int64_t plan_bytes;            /* the plan blob: what to upload */
+    int64_t reserved[3];           /* 0 */
+} ro_resize_info_t;
+
+/* The shape rule above.  Pure host.  RO_ERR_INVALID: width < 1, naxis1 < 1, naxis2 < 1, a null result. */
+int ro_resize_shape(int32_t naxis1, int64_t naxis2, int32_t width, int32_t *out_naxis1, int64_t *out_naxis2);
+
+/* The plan of one level directory.  Pure host; nothing of the levels is read.
+ *   level_dir, dir_capacity, level_summary   a HOST level directory and its summary: those of
+ *                    ro_stft_snapshot_levels_resident after a download, or of ro_periodic_level_dir; n = min(max(
+ *                    level_summary->entries, 0), dir_capacity)
+ *   levels_bytes     the room the directory's offsets are checked against
+ *   width            fits2png's --width
+ *   out_level_dir    room for dir_capacity entries; entry d describes level_dir[d], for d < n, in the family's form: offset
+ *                    is bytes into the out levels, a multiple of RO_LEVEL_BLOCK, bytes = naxis1 naxis2 of the RESIZED image
+ *   out_levels_bytes the room of the out levels
+ *   out_level_summary   one entry, as the levels' calls write it: units_bytes the end of the last written image's last
+ *                    block, needed_bytes the room that holds every writable one
+ *   plan, plan_bytes the blob (csrc/ro_resize.h), aligned to 8 bytes: one job per WRITTEN entry -- where its pixels are and
+ *                    go, its four sizes, its two tap tables -- and the tap tables with their xmin / xmax, one per distinct
+ *                    (in, out) pair, shared between axes and entries.  plan = NULL with plan_bytes = 0 is the SIZING form:
+ *                    everything but the blob is written, and info->plan_bytes is what the blob takes
+ *   info             one entry
+ * For entry d < n, in this order:
+ *   1  status != RO_UNIT_WRITTEN       RO_UNIT_SKIPPED
+ *   2  rule 2 of ro_stft_levels_png_resident (a shape that cannot be a PNG included: an image has fewer than 2^31 pixels)
+ *                                      RO_UNIT_INVALID
+ *   3  H' == 0                         RO_UNIT_SKIPPED: fits2png has no image to save
+ *   4  otherwise                       WRITABLE: naxis1 = W', naxis2 = H', bytes = W' H', blocks = ceil(bytes / 720)
+ * with the family's prefix rule over all writable entries: RO_UNIT_WRITTEN when offset + 720 blocks <= out_levels_bytes,
+ * otherwise RO_UNIT_NO_ROOM, carrying its shape with offset 0.  An image with width >= W is a job too, a plain copy, so
+ * that the out directory is complete.
+ * RO_ERR_INVALID, the text naming the argument: a negative dir_capacity, levels_bytes, out_levels_bytes or plan_bytes;
+ * width < 1; dir_capacity > 2^24; a null level_summary, out_level_dir, out_level_summary or info; level_dir == NULL with
+ * dir_capacity > 0; plan == NULL with plan_bytes > 0; plan not aligned to 8 bytes; plan_bytes > 0 (or a plan) that is less
+ * than the blob takes -- the outputs but the blob are written then, info->plan_bytes included. */
+int ro_resize_plan(const ro_fits_unit_t *level_dir, int64_t dir_capacity, const ro_unit_summary_t *level_summary,
+                   int64_t levels_bytes, int32_t width, ro_fits_unit_t *out_level_dir, int64_t out_levels_bytes,
+                   ro_unit_summary_t *out_level_summary, void *plan, int64_t plan_bytes, ro_resize_info_t *info);
+
+/* The resized images of one plan.
+ *   info             what ro_resize_plan wrote (HOST)
+ *   d_plan           the caller's upload of info->plan_bytes bytes of the blob, on the same stream, aligned to 16 bytes
+ *   d_levels, levels_bytes   the level images the planned directory describes, aligned to 16 bytes
+ *   d_out_levels, out_levels_bytes   the resized images, aligned to 16 bytes: every job's image at its entry's offset,
+ *                    zero-padded to its last 720-byte block.  Bytes past the out summary's units_bytes are not touched
+ * Two plain launches (csrc/ro_resize.hip: the horizontal pass; the vertical pass, with the copies of the images that keep
+ * their shape and the zero padding), no atomics, no floating point, no workgroup waiting for another: equal inputs give
+ * equal bytes.  The intermediate images live in handle scratch of this call's own (it grows, waiting for the device, with
+ * info->mid_bytes): one call in flight per handle unless they share a stream.  The sources are only read.  The blob is
+ * the caller's memory, so the kernels check every job against the four rooms before anything of it is touched and clamp
+ * every tap's bounds into its image: a job that does not fit is left out.  Asynchronous on `stream`.  info->jobs == 0
+ * launches nothing.
+ * RO_ERR_INVALID, before anything is launched, the text naming the argument: a null handle, info or d_plan; an info
+ * with a negative field; d_levels == NULL with levels_bytes > 0; d_out_levels == NULL with out_levels_bytes > 0; d_plan,
+ * d_levels or d_out_levels not aligned to 16 bytes; a negative levels_bytes or out_levels_bytes; [d_out_levels, +
+ * out_levels_bytes) overlapping the levels or the plan. */
+int ro_stft_levels_resize_resident(ro_stft_t *h, const ro_resize_info_t *info, const void *d_plan, const void *d_levels,
+                                   int64_t levels_bytes, void *d_out_levels, int64_t out_levels_bytes, void *stream);
+
+/* The same over host memory from the same plan, with int32 sums: no handle, no device.  The yardstick of the device
+ * call: equal inputs give equal bytes.  Refusals as above, without the handle, with 8 bytes for the plan's alignment and
+ * none for the images'; and a plan that is not the blob of info->plan_bytes bytes. */
+int ro_levels_resize_host(const ro_resize_info_t *info, const void *plan, const void *levels, int64_t levels_bytes,
+                          void *out_levels, int64_t out_levels_bytes);
 
 /* Times `iters` back-to-back launches of the resident path with HIP events on
  * the launch stream; ms_out[i] = duration of launch i (STFT kernel + scan kernel

@@ -27,6 +27,7 @@ from .capi import (  # noqa: F401
     PERIODIC_SUMMARY_DTYPE, RO_MAX_PERIODIC, RO_PERIODIC_WRITTEN, RO_PERIODIC_LOST, RO_PERIODIC_NO_ROOM,
     snapshot_levels_host, periodic_levels_host, LEVEL_RANGE_DTYPE, RO_LEVEL_BLOCK,
     png_bytes, levels_png_host, levels_png_deflate_host, periodic_level_dir, RO_PNG_ALIGN,
+    resize_shape, resize_plan, levels_resize_host, RESIZE_INFO_DTYPE,
     RO_WINDOW_NUTTALL, RO_WINDOW_HANN, RO_WINDOW_CUSTOM, RO_IQ_F32, RO_IQ_I16, RO_IQ_F64,
     RO_PRECISION_F32, RO_PRECISION_F64,
 )

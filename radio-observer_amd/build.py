@@ -10,9 +10,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libro_stft.so")
-SOURCES = ["ro_kernels.hip", "ro_stft32k.hip", "ro_fourstep.hip", "ro_f64reg.hip", "ro_band.hip", "ro_band_f64.hip", "ro_band_windows.hip", "ro_band_windows_f64.hip", "ro_scan_sets.hip", "ro_cut_windows.hip", "ro_events.hip", "ro_snapshots.hip", "ro_raw.hip", "ro_units.hip", "ro_periodic.hip", "ro_levels.hip", "ro_png.hip", "ro_png_deflate.hip", "ro_stft_capi.cpp", "ro_abi_helpers.cpp",
-           "ro_exchange.cpp", "ro_stream.cpp", "ro_czt.cpp", "ro_snapshots.cpp", "ro_raw.cpp", "ro_units.cpp", "ro_periodic.cpp", "ro_levels.cpp", "ro_png.cpp", "ro_png_deflate.cpp"]
-HEADERS = ["ro_kernels.h", "ro_band.h", "ro_band_f64.h", "ro_band_windows.h", "ro_events.h", "ro_snapshots.h", "ro_raw.h", "ro_units.h", "ro_periodic.h", "ro_levels.h", "ro_png.h", "ro_png_deflate.h", "ro_png_crc_device.h", "ro_pack_plan.h", "ro_host.h", "ro_owned.h", "ro_fft_device.h", "ro_fft_planar.h", "ro_k32_lds.h", "ro_device_util.h", "ro_f64_device.h", "ro_narrow.h", os.path.join("..", "..", "include", "ro_stft.h")]
+SOURCES = ["ro_kernels.hip", "ro_stft32k.hip", "ro_fourstep.hip", "ro_f64reg.hip", "ro_band.hip", "ro_band_f64.hip", "ro_band_windows.hip", "ro_band_windows_f64.hip", "ro_scan_sets.hip", "ro_cut_windows.hip", "ro_events.hip", "ro_snapshots.hip", "ro_raw.hip", "ro_units.hip", "ro_periodic.hip", "ro_levels.hip", "ro_png.hip", "ro_png_deflate.hip", "ro_resize.hip", "ro_stft_capi.cpp", "ro_abi_helpers.cpp",
+           "ro_exchange.cpp", "ro_stream.cpp", "ro_czt.cpp", "ro_snapshots.cpp", "ro_raw.cpp", "ro_units.cpp", "ro_periodic.cpp", "ro_levels.cpp", "ro_png.cpp", "ro_png_deflate.cpp", "ro_resize.cpp"]
+HEADERS = ["ro_kernels.h", "ro_band.h", "ro_band_f64.h", "ro_band_windows.h", "ro_events.h", "ro_snapshots.h", "ro_raw.h", "ro_units.h", "ro_periodic.h", "ro_levels.h", "ro_png.h", "ro_png_deflate.h", "ro_resize.h", "ro_png_crc_device.h", "ro_pack_plan.h", "ro_host.h", "ro_owned.h", "ro_fft_device.h", "ro_fft_planar.h", "ro_k32_lds.h", "ro_device_util.h", "ro_f64_device.h", "ro_narrow.h", os.path.join("..", "..", "include", "ro_stft.h")]
 
 # -fno-slp-vectorize: the SLP vectoriser turns the twiddle multiplies into v_pk_* ops whose
 # constant operands must sit in VGPR pairs; that costs ~28 VGPRs and makes the 1024-thread

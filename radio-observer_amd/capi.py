@@ -133,6 +133,9 @@ PERIODIC_SUMMARY_DTYPE = np.dtype([("entries", np.int64), ("written", np.int64),
 RO_LEVEL_BLOCK = 720
 # ro_level_range_t (8 bytes: the colour range of one level image)
 LEVEL_RANGE_DTYPE = np.dtype([("ln_min", np.float32), ("ln_max", np.float32)])
+# ro_resize_info_t (64 bytes: the host scalars of one resize plan)
+RESIZE_INFO_DTYPE = np.dtype([("jobs", np.int64), ("h_items", np.int64), ("v_items", np.int64), ("mid_bytes", np.int64),
+                              ("plan_bytes", np.int64), ("reserved", np.int64, (3,))])
 
 
 class Config(C.Structure):
@@ -276,6 +279,12 @@ _EXPORTS = {
     "ro_levels_png_deflate_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                              C.c_int64, C.c_void_p]),
     "ro_periodic_level_dir": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ro_resize_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ro_resize_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                 C.c_void_p, C.c_int64, C.c_void_p]),
+    "ro_stft_levels_resize_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                 C.c_void_p]),
+    "ro_levels_resize_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "ro_stft_time_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -837,6 +846,51 @@ def periodic_level_dir(directory):
     return level_dir[:len(directory)], out[0]
 
 
+def resize_shape(naxis1, naxis2, width):
+    """The shape fits2png's --width gives a naxis1 x naxis2 image -- ro_resize_shape: (width, int(naxis2 * (width / naxis1)))
+    where width < naxis1, the image's own shape otherwise.  The height can be 0."""
+    w, h = C.c_int32(), C.c_int64()
+    _check(library().ro_resize_shape(int(naxis1), int(naxis2), int(width), C.byref(w), C.byref(h)))
+    return w.value, h.value
+
+
+def resize_plan(level_dir, level_summary, levels_bytes, width, out_levels_bytes, dir_capacity=None):
+    """The plan that resizes every level image of a HOST level directory to `width` -- ro_resize_plan, its sizing form first.
+    level_dir / level_summary as levels_png_host takes them; levels_bytes: the room their offsets are checked against;
+    out_levels_bytes: the room of the resized images.  Returns (out directory, out summary, plan, info): FITS_UNIT_DTYPE
+    entries and a UNIT_SUMMARY_DTYPE scalar in the levels' form, for levels_png_host and Stft.levels_png_resident to read;
+    the blob as uint8 [info.plan_bytes], to upload; a RESIZE_INFO_DTYPE array of one entry."""
+    level_dir = np.ascontiguousarray(level_dir)
+    level_summary = np.ascontiguousarray(level_summary).reshape(-1)
+    if level_dir.dtype != FITS_UNIT_DTYPE or level_dir.ndim != 1 or level_summary.dtype != UNIT_SUMMARY_DTYPE or level_summary.size < 1:
+        raise ValueError("level_dir: FITS_UNIT_DTYPE [n] with the UNIT_SUMMARY_DTYPE of the call that wrote them")
+    dcap = level_dir.shape[0] if dir_capacity is None else dir_capacity
+    out_dir = np.zeros(max(dcap, 1), FITS_UNIT_DTYPE)
+    out = np.zeros(1, UNIT_SUMMARY_DTYPE)
+    info = np.zeros(1, RESIZE_INFO_DTYPE)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    args = (p(level_dir) if dcap else None, dcap, p(level_summary), int(levels_bytes), int(width), p(out_dir), int(out_levels_bytes), p(out))
+    _check(library().ro_resize_plan(*args, None, 0, p(info)))
+    plan = np.zeros(int(info["plan_bytes"][0]) // 8, np.int64).view(np.uint8)
+    _check(library().ro_resize_plan(*args, p(plan), plan.size, p(info)))
+    return out_dir[:int(out["entries"][0])], out[0], plan, info
+
+
+def levels_resize_host(info, plan, levels, out_levels_bytes):
+    """The resized images of one plan over host memory -- ro_levels_resize_host.  info, plan: what resize_plan returned;
+    levels: uint8, the images the planned directory describes.  Returns the out levels, uint8 [out_levels_bytes]: every
+    written entry's image at its offset, zero-padded to its last 720-byte block."""
+    info = np.ascontiguousarray(info).reshape(-1)
+    plan, levels = np.ascontiguousarray(plan), np.ascontiguousarray(levels)
+    if info.dtype != RESIZE_INFO_DTYPE or info.size < 1 or plan.dtype != np.uint8 or levels.dtype != np.uint8 or levels.ndim != 1:
+        raise ValueError("info: RESIZE_INFO_DTYPE; plan, levels: uint8")
+    out = np.zeros(max(out_levels_bytes, 1), np.uint8)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    _check(library().ro_levels_resize_host(p(info), p(plan), p(levels) if levels.size else None, levels.size,
+                                           p(out) if out_levels_bytes > 0 else None, out_levels_bytes))
+    return out[:out_levels_bytes]
+
+
 def device_count():
     n = library().ro_device_count()
     if n < 0:
@@ -1094,6 +1148,17 @@ class Stft:
         _check(library().ro_stft_levels_png_deflate_resident(self._h, _ptr(d_level_dir), dir_capacity, _ptr(d_level_summary),
                                                              _ptr(d_levels), levels_bytes, _ptr(d_png_dir), _ptr(d_png),
                                                              png_bytes, _ptr(d_png_summary), _ptr(stream)))
+
+    def levels_resize_resident(self, info, d_plan, d_levels, levels_bytes, d_out_levels, out_levels_bytes, stream=None):
+        """Every level image a resize plan has a job for, resized as fits2png's --width does (Pillow's Lanczos, to the byte),
+        at its out entry's offset of d_out_levels: two launches -- ro_stft_levels_resize_resident.  info: what resize_plan
+        returned (HOST); d_plan: the upload of its blob, on the same stream; d_levels / d_out_levels: aligned to 16.  The out
+        directory and summary are resize_plan's: upload them for levels_png_resident"""
+        info = np.ascontiguousarray(info).reshape(-1)
+        if info.dtype != RESIZE_INFO_DTYPE or info.size < 1:
+            raise ValueError("info: RESIZE_INFO_DTYPE")
+        _check(library().ro_stft_levels_resize_resident(self._h, C.c_void_p(info.ctypes.data), _ptr(d_plan), _ptr(d_levels),
+                                                        levels_bytes, _ptr(d_out_levels), out_levels_bytes, _ptr(stream)))
 
     def scan_sets_resident(self, d_rows, rows, d_extra, d_records=None, row_stride=None, stream=None):
         """scan_resident for the extra sets (and the primary too when d_records is given)"""

@@ -16,6 +16,8 @@
 //                        twins of both kinds of file over it, and a periodic plan's directory in level form
 //   ro_png_deflate.cpp   the same files with Huffman-coded deflate blocks (ro_png_deflate.hip), and a block's code and its
 //                        bytes on the host, in either form
+//   ro_resize.cpp        the level images resized to a width, Pillow's Lanczos to the byte (ro_resize.hip): the plan with
+//                        its tap tables (host arithmetic), the launches, and the host twin
 // Said once, here: pack_walk, the walk of every host twin that packs a source directory into a buffer (the units, the level
 // images, both kinds of file), and scratch_for (ro_stft_capi.cpp), the prelude of every plan-then-copy call.
 // ro_owned.h has the type that owns every device and pinned block of the handle, its slots and its batches.
@@ -52,6 +54,7 @@
 #include "ro_levels.h"
 #include "ro_png.h"
 #include "ro_png_deflate.h"
+#include "ro_resize.h"
 #include "ro_narrow.h"
 #include "ro_owned.h"
 
@@ -294,6 +297,9 @@ struct ro_stft {
     // compressed preview files (ro_stft_levels_png_deflate_resident): the plan, every block's size, code table and checksum
     // parts of one call (ro_png_deflate.h); grows with dir_capacity and with levels_bytes
     DeviceBlock<char> d_png_deflate_scratch;
+    // resized previews (ro_stft_levels_resize_resident): the intermediate images between the two passes of one call
+    // (ro_resize.h); grows with the plan's mid_bytes
+    DeviceBlock<char> d_resize_scratch;
     int cus = 0;                               // the device's compute units (device_cus; 0: not asked for yet)
 
     // band-only transform (ro_stft_band_resident, ro_stft_band_windows_resident): band_key is the window list the tables
